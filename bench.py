@@ -19,8 +19,13 @@ already running under torch.distributed.run.
 The JSON line also carries
   roofline      the kernel with the largest device time and a per-kernel table: algorithmic bytes / HIP-event time vs 8 TB/s for the
                 HBM-bound kernels, evaluated DP cells per second for the DP kernels
-  cpu_baseline  the REFERENCE's own C (oracle/_ref/libmm2ref.so, compiled from /root/reference by oracle/Makefile), one process
+A plain run sets up, warms up, times --steps steps and prints the line; --dump-outputs DIR also writes the records the last timed step
+returned (dump_outputs).  Everything else runs after the timed steps under --full only:
+  parity        every call of the last timed step against the compiled reference's digests (no value on a mismatch), build_sha256
+  resident_gbp_s  one more step with the inputs already resident in HBM (N = 1)
+  cpu_baseline  the REFERENCE's own C (oracle/_ref/libmm2ref.so, compiled from the reference's sources by oracle/Makefile), one process
                 per host core, on a bounded sample of the same waves
+  detail file   per-kernel table, batch timeline, stage sums, predicted scaling, the SURVEY 8(f) rows (also written when --detail is given)
 """
 import argparse
 import json
@@ -306,6 +311,54 @@ def next_rows(pop, seed: int):
     return out
 
 
+# the fields of a record (pangraph_amd.dist.MATCH_DTYPE) a caller reads, in the record's order; cigar_off and pad only say where in the pool
+DUMP_FIELDS = ("qry", "ref", "qry_len", "qry_start", "qry_end", "ref_len", "ref_start", "ref_end", "matches", "length", "quality", "reverse",
+               "align", "n_ambi", "inv", "divergence", "n_cigar")
+
+
+def dump_outputs(results, n_calls: int, out_dir: str, seed: int, budget: int = 64 << 20):
+    """What the last timed step returned, as float64 .npy files in out_dir (every field and CIGAR word is exact in float64):
+      records_per_call.npy  [n_calls]          records of each find_matches call, in task order
+      matches.npy           [n_records, 18]    task id of the call, then DUMP_FIELDS; calls in task order, a call's records in the aligner's order
+      cigars.npy            [n_ops]            the CIGAR words (length << 4 | op) of those records, one after the other
+    The order does not depend on which batch finished first.  If matches + cigars would exceed the budget, they hold the calls of a fixed,
+    seeded sample of the task ids only.  results: per batch (tasks, records with group = index into tasks, CIGAR pool, covered) as the
+    parity check reads them."""
+    import numpy as np
+    tids, recs, pools, base = [], [], [], 0
+    for ts, rec, pool, covered in results:
+        if not len(rec):
+            continue
+        keep = np.ones(len(rec), bool) if covered is None else np.isin(rec["group"], np.asarray(covered, dtype=np.int64))
+        rec = rec[keep]
+        tids.append(np.asarray([t.tid for t in ts], dtype=np.int64)[rec["group"]])
+        off = rec["cigar_off"].astype(np.int64) + base
+        recs.append((rec, off))
+        pools.append(np.asarray(pool).view(np.uint32))
+        base += len(pools[-1])
+    tid = np.concatenate(tids) if tids else np.zeros(0, np.int64)
+    order = np.argsort(tid, kind="stable")
+    per_call = np.bincount(tid, minlength=n_calls).astype(np.float64)
+    cols = [tid.astype(np.float64)] + [np.concatenate([r[f] for r, _ in recs]).astype(np.float64) if recs else np.zeros(0) for f in DUMP_FIELDS]
+    mat = np.stack(cols, axis=1)[order]
+    n_cig = np.concatenate([r["n_cigar"] for r, _ in recs]).astype(np.int64)[order] if recs else np.zeros(0, np.int64)
+    off = np.concatenate([o for _, o in recs])[order] if recs else np.zeros(0, np.int64)
+    pool = np.concatenate(pools) if pools else np.zeros(0, np.uint32)
+    picked = np.arange(n_calls)
+    while mat.nbytes + 8 * int(n_cig.sum()) + per_call.nbytes > budget and len(picked) > 1:
+        picked = np.sort(np.random.default_rng(seed).permutation(n_calls)[:len(picked) // 2])
+        sel = np.isin(mat[:, 0].astype(np.int64), picked)
+        mat, n_cig, off = mat[sel], n_cig[sel], off[sel]
+    starts = np.cumsum(n_cig) - n_cig
+    idx = np.arange(int(n_cig.sum()), dtype=np.int64) - np.repeat(starts, n_cig) + np.repeat(off, n_cig)
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "records_per_call.npy"), per_call)
+    np.save(os.path.join(out_dir, "matches.npy"), mat)
+    np.save(os.path.join(out_dir, "cigars.npy"), pool[idx].astype(np.float64))
+    print(f"bench.py: outputs of the last timed step in {out_dir}: {len(mat)} records of {len(picked)} of {n_calls} calls, {len(idx)} CIGAR words",
+          file=sys.stderr)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -315,24 +368,33 @@ def main():
     ap.add_argument("--length", type=int, default=int(os.environ.get("PGA_BENCH_LENGTH", 5_000_000)))
     ap.add_argument("--seed", type=int, default=20260928)
     ap.add_argument("--leaf-only", action="store_true", help="diagnosis: only the waves of height 1")
-    ap.add_argument("--cpu-budget", type=float, default=20.0, help="seconds of CPU-baseline work per core (0 disables)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check what the headline does not need, after the timed steps: the parity of the last timed step against the "
+                         "reference digests, build_sha256, the resident-input rate, the CPU baseline, the SURVEY 8(f) rows and the detail file")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned (records of every call in task order, their CIGARs) to DIR/*.npy, float64, at most 64 MB")
+    ap.add_argument("--cpu-budget", type=float, default=20.0, help="--full: seconds of CPU-baseline work per core (0 disables)")
     ap.add_argument("--schedule", choices=("ready", "waves"), default=os.environ.get("PGA_BENCH_SCHEDULE", "ready"),
                     help="ready: a find_matches call starts when the calls it depends on are done (pangraph_amd/schedule.py); waves: level-synchronous, one batch per wave")
     ap.add_argument("--inputs", choices=("resident", "host"), default=os.environ.get("PGA_BENCH_INPUTS", "host"),
                     help="host (default, SURVEY 8d): every call hands over host strings inside the timed region (H2D + encoding are timed); resident: the block "
                          "sequences of every call are in HBM (packed store) before the timed region, a call takes its inputs by a device-to-device copy "
-                         "(pga_batch_derive) -- reported as the secondary `resident_gbp_s` by a default run")
-    ap.add_argument("--detail", default=os.environ.get("PGA_BENCH_DETAIL", os.path.join(ROOT, "bench_detail.json")),
-                    help="where the long form goes (per-kernel table, batch timeline, stage sums, next rows); the LAST line of stdout stays under 4 KB")
-    ap.add_argument("--no-resident-rate", action="store_true", help="skip the one extra step with resident inputs after the timed region (N = 1)")
-    ap.add_argument("--no-parity-check", action="store_true", help="do not digest the last timed step's records against tests/golden/builds_expected.json.gz")
+                         "(pga_batch_derive) -- reported as the secondary `resident_gbp_s` by a --full run")
+    ap.add_argument("--detail", default=os.environ.get("PGA_BENCH_DETAIL"),
+                    help="where the long form goes (per-kernel table, batch timeline, stage sums, next rows); written when given, and by --full "
+                         "(default there: bench_detail.json in the repository root); the LAST line of stdout stays under 4 KB")
+    ap.add_argument("--no-resident-rate", action="store_true", help="--full: skip the one extra step with resident inputs after the timed region (N = 1)")
+    ap.add_argument("--no-parity-check", action="store_true", help="--full: do not digest the last timed step's records against tests/golden/builds_expected.json.gz")
     ap.add_argument("--model-gbp-s", type=float, default=7.9, help="N > 1: single-GPU rate the scaling model is evaluated with (profiles/r05_d_bench_c5.json)")
     ap.add_argument("--model-host-s-per-gbp", type=float, default=0.85, help="N > 1: host core-seconds per Gbp of the single-GPU run (14.5 s per 17.07 Gbp step)")
     ap.add_argument("--slots", type=int, default=int(os.environ.get("PGA_BENCH_SLOTS", 6)), help="batches in flight (ready-set schedule)")
     ap.add_argument("--express", type=int, default=int(os.environ.get("PGA_BENCH_EXPRESS", 0)), help="slots reserved for the calls on the longest remaining path (schedule.run_ready_set: express)")
     ap.add_argument("--cap-gbp", type=float, default=float(os.environ.get("PGA_BENCH_CAP_GBP", 1.2)), help="largest batch of the ready-set schedule")
-    ap.add_argument("--no-next-rows", action="store_true", help="skip the one-off timings of the SURVEY 8(f) rows (guide tree, map_variations) reported next to the headline")
+    ap.add_argument("--no-next-rows", action="store_true", help="--full: skip the one-off timings of the SURVEY 8(f) rows (guide tree, map_variations) reported next to the headline")
     args = ap.parse_args()
+    if args.dump_outputs and args.schedule != "ready":
+        raise SystemExit("bench.py: --dump-outputs needs --schedule ready (the level-synchronous schedule does not keep the records of a step)")
+    detail_path = args.detail or (os.path.join(ROOT, "bench_detail.json") if args.full else None)
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         respawn_under_torchrun(args.gpus)
@@ -441,7 +503,7 @@ def main():
     # after them, its construction (17 GB of temporaries) lands on a cache the steps have filled and the allocator starts giving blocks back --
     # hipFree synchronises the device and the following steps ran 1.6x slower (measured; pga_mem_stats shows it)
     stash = None
-    want_secondary = world == 1 and args.schedule == "ready" and inp["lib"] is None and not args.no_resident_rate and not args.leaf_only
+    want_secondary = args.full and world == 1 and args.schedule == "ready" and inp["lib"] is None and not args.no_resident_rate and not args.leaf_only
     if want_secondary:
         make_resident(); stash = dict(inp); inp.update({"lib": None, "first": None})
 
@@ -610,9 +672,11 @@ def main():
 
     # ---- parity of the step that was timed: every find_matches call of the LAST timed step against the digests the compiled reference
     # produced for this build (tests/golden/builds_expected.json.gz).  A differing call means the number is not a measurement of the path.
-    parity = {"parity_checked_calls": 0, "parity": "not checked"}
+    parity = {"parity_checked_calls": 0, "parity": "not checked" if args.full else "not checked (--full checks it)"}
     build_sha = None
-    if rank == 0 and args.schedule == "ready" and not args.leaf_only and last.get("results"):
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(last["results"], len(tasks), args.dump_outputs, args.seed)
+    if args.full and rank == 0 and args.schedule == "ready" and not args.leaf_only and last.get("results"):
         # one digest of the whole build's record lists (sha256 over the per-call digests in call order): equal for any number of ranks
         import hashlib
         from pangraph_amd import digest as dg
@@ -622,7 +686,7 @@ def main():
             for i in (range(len(ts)) if covered is None else covered):
                 per_call[ts[i].tid] = (len(lists[i]), dg.digest(lists[i]))
         build_sha = hashlib.sha256(json.dumps([per_call[k] for k in sorted(per_call)]).encode()).hexdigest() if len(per_call) == len(tasks) else None
-    if rank == 0 and args.schedule == "ready" and not args.no_parity_check and not args.leaf_only:
+    if args.full and rank == 0 and args.schedule == "ready" and not args.no_parity_check and not args.leaf_only:
         from pangraph_amd import digest as dg
         gold = dg.expected_build(args.seed, args.genomes, args.length)
         if gold is None:
@@ -780,7 +844,7 @@ def main():
         "host_cpu": {"cpu_s_per_step": host_cpu_s / args.steps, "system_s_per_step": (cpu1.system - cpu0.system) / args.steps, "mean_busy_cores": host_cpu_s / dt, "usable_cores": usable_cpus(), "threads_per_batch": slot_threads},
         "resident_inputs": resident,
         "predicted_scaling": (sched.predict_scaling(pop, tasks, (1, 2, 4, 8), units * args.steps / dt / 1e9, args.slots, host_cpu_s_per_gbp=host_cpu_s / args.steps / (units / 1e9),
-                                                    host_cores=usable_cpus()) if world == 1 and args.schedule == "ready" and not args.leaf_only else None),
+                                                    host_cores=usable_cpus()) if detail_path and world == 1 and args.schedule == "ready" and not args.leaf_only else None),
         "traffic_source": "profiles/ (rocprofv3 --pmc passes of this workload, not this run); bytes per launch in the unit of alg_bytes_per_launch",
     }
     if world > 1 and args.schedule == "ready" and last.get("phases"):
@@ -793,12 +857,12 @@ def main():
                                   "model_inputs": {"gbp_s_one_gpu": args.model_gbp_s, "host_cpu_s_per_gbp": args.model_host_s_per_gbp, "host_cores": usable_cpus()},
                                   "single_device": bool(os.environ.get("PGA_BENCH_SINGLE_DEVICE"))}
     if rank == 0:
-        if args.cpu_budget > 0 and world == 1:
+        if args.full and args.cpu_budget > 0 and world == 1:
             out["cpu_baseline"] = cpu_baseline(waves, args.cpu_budget)
             detail["cpu_baseline_one_core_gbp_s"] = out["cpu_baseline"].pop("one_core_gbp_s", None)
-        elif world > 1:
+        elif args.full and world > 1:
             out["cpu_baseline"] = {"value": None, "unit": "Gbp/s", "cores": 0, "kind": "reference", "sample": "measured at N=1 only"}
-        if world == 1 and not args.no_next_rows:
+        if args.full and world == 1 and not args.no_next_rows:
             detail["next_rows"] = next_rows(pop, args.seed)
         line = json.dumps(out)
         if len(line) > 4000:                                       # the driver parses ONE short line: drop the prose first
@@ -806,11 +870,12 @@ def main():
             out["config"].pop("parallelism", None)
             line = json.dumps(out)
         detail["bench_line"] = out
-        try:
-            with open(args.detail, "w") as f:
-                json.dump(detail, f, indent=1)
-        except OSError as e:
-            print(f"bench.py: detail not written: {e}", file=sys.stderr)
+        if detail_path:
+            try:
+                with open(detail_path, "w") as f:
+                    json.dump(detail, f, indent=1)
+            except OSError as e:
+                print(f"bench.py: detail not written: {e}", file=sys.stderr)
         print(line, flush=True)
     if world > 1:
         dist.destroy_process_group()

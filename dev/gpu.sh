@@ -34,6 +34,7 @@ tests)
   timeout ${T:-2400} python -m pytest tests -m gpu -x -q --timeout 1500 "$@" 2>&1 | tail -${TAILN:-8} ;;
 bench)
   name=$1; shift
+  set -- --full "$@"      # the whole line: parity of the timed step, resident rate, CPU baseline, detail file
   timeout ${T:-900} python bench.py --detail gpurun_out/${name}_detail.json "$@" > gpurun_out/$name.json 2> gpurun_out/$name.err; echo "bench rc=$?"
   tail -3 gpurun_out/$name.err; summ gpurun_out/$name.json ;;
 ab)

@@ -37,10 +37,9 @@ def ref_lib():
     """The reference's own C, compiled by oracle/Makefile (prebuilt .so on the GPU box)."""
     from pangraph_amd.mm2ffi import Mm2Lib
     if not os.path.exists(REF_SO):
-        if os.path.isdir("/root/reference"):
-            _make(os.path.join(ROOT, "oracle"), "ref")
-        else:
-            pytest.skip("oracle/_ref/libmm2ref.so not built and /root/reference absent")
+        _make(os.path.join(ROOT, "oracle"), "ref")          # builds it where the reference's sources are present (oracle/Makefile: REF)
+        if not os.path.exists(REF_SO):
+            pytest.skip("oracle/_ref/libmm2ref.so not built and the reference's sources absent")
     return Mm2Lib(REF_SO)
 
 

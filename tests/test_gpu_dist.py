@@ -248,7 +248,7 @@ def test_bench_c5_two_ranks_on_one_device_every_call_vs_reference_digests():
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = dict(os.environ, PGA_BENCH_SINGLE_DEVICE="1")
-    cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "1", "--warmup", "0", "--cpu-budget", "0", "--no-next-rows",
+    cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "1", "--warmup", "0", "--full", "--cpu-budget", "0", "--no-next-rows",
            "--detail", os.path.join(root, "gpurun_out", "bench_detail_2ranks.json")]
     os.makedirs(os.path.join(root, "gpurun_out"), exist_ok=True)
     two = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=1500)
@@ -268,7 +268,7 @@ def test_bench_eight_ranks_on_one_device_equals_the_single_rank_build():
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = dict(os.environ, PGA_BENCH_SINGLE_DEVICE="1")
-    common = ["--genomes", "40", "--length", "60000", "--steps", "1", "--warmup", "0", "--cpu-budget", "0", "--no-next-rows", "--no-resident-rate"]
+    common = ["--genomes", "40", "--length", "60000", "--steps", "1", "--warmup", "0", "--full", "--cpu-budget", "0", "--no-next-rows", "--no-resident-rate"]
     os.makedirs(os.path.join(root, "gpurun_out"), exist_ok=True)
     outs = {}
     for n in (1, 8):
@@ -294,7 +294,7 @@ def test_bench_c5_eight_ranks_on_one_device_every_call_vs_reference_digests_and_
     env = dict(os.environ, PGA_BENCH_SINGLE_DEVICE="1")
     det = os.path.join(root, "gpurun_out", "bench_detail_8ranks_c5.json")
     os.makedirs(os.path.join(root, "gpurun_out"), exist_ok=True)
-    cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "8", "--steps", "1", "--warmup", "0", "--cpu-budget", "0", "--no-next-rows", "--detail", det]
+    cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "8", "--steps", "1", "--warmup", "0", "--full", "--cpu-budget", "0", "--no-next-rows", "--detail", det]
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=1500)
     assert r.returncode == 0, (r.stdout[-1500:], r.stderr[-2000:])
     b = json.loads(r.stdout.strip().splitlines()[-1])
