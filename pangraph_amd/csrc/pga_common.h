@@ -10,7 +10,9 @@
 #include <algorithm>
 #include <stdint.h>
 #include <stddef.h>
+#include <mutex>
 #include <string>
+#include <utility>
 #include <vector>
 #include <stdexcept>
 #include "../../include/pga_mm2_abi.h"
@@ -137,7 +139,19 @@ struct PkBases {
 		const uint32_t mm = (uint32_t)nmask[i] | (uint32_t)nmask[i + 1] << 16;
 		m = (mm >> sft) & 0xffffu;
 	}
+	static __device__ __forceinline__ int complement(int c) { return c < 4 ? 3 - c : 4; }   // of a base code
 };
+
+// A kernel's ceiling of dynamic LDS is a per-DEVICE function attribute: set once per kernel and device, whatever thread comes first.
+inline void set_max_dynamic_lds_once(const void *kernel, size_t bytes)
+{
+	static std::mutex mu; static std::vector<std::pair<const void*, int>> done;
+	int dev = 0; PGA_HIP(hipGetDevice(&dev));
+	std::lock_guard<std::mutex> lk(mu);
+	for (const auto &d : done) if (d.first == kernel && d.second == dev) return;
+	PGA_HIP(hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
+	done.emplace_back(kernel, dev);
+}
 
 struct SeqSet {
 	int n_seq = 0;

@@ -33,6 +33,12 @@ struct DpRes {           // ksw_extz_t (ksw2.h:31-40)
 struct DpParams { int32_t q, e, q2, e2, sc_mch, sc_mis, sc_ambi; int32_t lb_mode; }; // sc_* are matrix entries mat[0], mat[1], mat[24]; lb_mode: 0 = the length-bound stop
                                                                                           // (below) is on, 1 = off, 2 = checked (the sweep goes on and the outcome is compared)
 
+} // namespace pga
+
+#include "pga_ksw_shared.h"   // the flag bits and limits named below; the device-side pieces the DP kernels share (they need the descriptors above)
+
+namespace pga {
+
 // The LENGTH-BOUND STOP of an extension whose target window is the few bases left before a block end (tlen <= 64; the bounds below close up to
 // tlen ~ 50 with the asm10 scores) while the query runs on for
 // kilobases: the reference sweeps ~w + 2 tlen diagonals until the band has slid past the last target column (ksw2_extd2_sse.c:172: st > en ->
@@ -55,7 +61,7 @@ __host__ __device__ inline int32_t lb_gap(int q, int e, int q2, int e2, int L) {
 __host__ __device__ inline LbStop lb_stop_of(int qlen, int tlen, int w, int flag, int q, int e, int q2, int e2, int sc_mch, int sc_mis, int sc_N, int lb_mode)
 {
 	LbStop S; S.on = 0; S.r_lo = S.r_hi = S.tail = 0;
-	if (lb_mode == 1 || (flag & (0x08 | 0x8000)) || tlen > 64 || tlen < 1 || w < 64 || qlen < w + 2 * tlen) return S;
+	if (lb_mode == 1 || (flag & (EZ_APPROX_MAX | PGA_JOB_LL)) || tlen > 64 || tlen < 1 || w < 64 || qlen < w + 2 * tlen) return S;
 	if (sc_mch < 0 || sc_mis > sc_mch || sc_N > sc_mch || q < 0 || e < 0 || q2 < 0 || e2 < 0) return S;
 	S.on = 1; S.r_lo = 2 * tlen; S.r_hi = w + 30;
 	const int qe1 = q + e < q2 + e2 ? q + e : q2 + e2;
@@ -71,5 +77,60 @@ __host__ __device__ inline bool lb_final(const LbStop &S, int r, int tlen, int q
 int dp_lb_mode();          // PGA_LB=off: 1, PGA_LB=check: 2 (read on every call: tests switch it inside one process), else 0
 size_t dp_slab_bytes(int qlen, int tlen, int w);
 void dp_run(PkBases d_bases, const std::vector<DpJob> &jobs, const DpParams &P, std::vector<DpRes> &res, PinVec<uint32_t> &cigars, hipStream_t st, Timers *tm = nullptr);
+
+// ---- the kernel classes of dp_run (pga_ksw.hip: dp_class): launchers, eligibility tests and scratch sizes, each defined beside its kernel ----
+void launch_extd2_fast(int C, unsigned n_waves, const DpJob *jobs, uint32_t n_jobs, PkBases bases, const DpParams &P, uint32_t *counter, uint8_t *slab, size_t slab_bytes,
+                       DpRes *res, uint32_t *pool, unsigned long long *cursor, unsigned long long pool_cap, hipStream_t st);
+
+size_t wide_lds_bytes(int r_cap, int seq_cap, bool exact);
+void launch_extd2_wide(unsigned n_blocks, int n_threads, int r_cap, int seq_cap, bool exact, const DpJob *jobs, uint32_t n_jobs, PkBases bases, const DpParams &P, uint32_t *counter, uint8_t *slab, size_t slab_bytes,
+                       DpRes *res, uint32_t *pool, unsigned long long *cursor, unsigned long long pool_cap, hipStream_t st);
+
+size_t ll_lds_bytes(int t_cap);
+size_t ll_multi_scratch_bytes();
+int ll_groups(uint32_t n_jobs, int t_max);
+void launch_ll_multi(int G, int t_cap, const DpJob *jobs, uint32_t n_jobs, PkBases bases, const DpParams &P, unsigned long long *scratch, DpRes *res, hipStream_t st);
+void launch_ll_i16(unsigned n_blocks, int t_cap, const DpJob *jobs, uint32_t n_jobs, PkBases bases, const DpParams &P, uint32_t *counter,
+                   unsigned long long *rowkey, size_t rowkey_stride, DpRes *res, hipStream_t st);
+
+size_t band_slab_bytes(int max_diag);
+void launch_gapfill_band(unsigned n_waves, const DpJob *jobs, uint32_t n_jobs, PkBases bases, const DpParams &P, uint32_t *counter, uint8_t *slab, size_t slab_bytes,
+                         DpRes *res, uint32_t *pool, unsigned long long *cursor, unsigned long long pool_cap, hipStream_t st);
+
+bool strips_eligible(const DpJob &j, const DpParams &P);
+size_t strips_slab_bytes(const DpJob &j);
+int strips_count(const DpJob &j);
+size_t strips_bnd_words(const DpJob &j);
+void launch_approx_strips(unsigned n_blocks, const DpJob *jobs, const uint32_t *blk_job, const uint32_t *blk_strip, PkBases bases, const DpParams &P, uint8_t *slab, const uint64_t *slab_off,
+                          uint32_t *bnd, const uint64_t *bnd_off, uint32_t *done_ctr, DpRes *res, uint32_t *pool, unsigned long long *cursor, unsigned long long pool_cap, hipStream_t st);
+
+bool wstrips_on();
+bool wstrips_eligible(const DpJob &j, const DpParams &P);
+int wstrips_count(const DpJob &j);
+size_t wstrips_bnd_words(const DpJob &j);
+void launch_wstrips(unsigned n_blocks, const DpJob *jobs, const uint32_t *blk_job, const uint32_t *blk_strip, PkBases bases, const DpParams &P, uint8_t *slab, const uint64_t *slab_off,
+                    unsigned long long *bnd, const uint64_t *bnd_off, uint32_t *done_ctr, DpRes *res, uint32_t *pool, unsigned long long *cursor, unsigned long long pool_cap, hipStream_t st);
+int bstrips_mode();
+int bstrips_max_problems();
+int bstrips_long_diagonals();
+bool bstrips_eligible(const DpJob &j, const DpParams &P);
+size_t bstrips_slab_bytes(const DpJob &j);
+size_t bstrips_words(const DpJob &j);
+uint32_t bstrips_table(const DpJob &j, std::vector<uint32_t> &tab, size_t *words);
+void launch_bstrips(unsigned n_blocks, const DpJob *jobs, const uint32_t *blk_job, PkBases bases, const DpParams &P, uint8_t *slab, const uint64_t *slab_off,
+                    unsigned long long *bnd, const uint64_t *bnd_off, const uint32_t *tab, const uint64_t *tab_off, DpRes *res, uint32_t *pool, unsigned long long *cursor,
+                    unsigned long long pool_cap, hipStream_t st);
+bool pipe_eligible(const DpJob &j);
+int pipe_mode();
+size_t pipe_cig_bytes(int q_cap, int t_cap);
+size_t pipe_chunk_bytes();
+int pipe_max_chunks();
+void launch_ext_pipe(unsigned n_blocks, int q_cap, int t_cap, const DpJob *jobs, uint32_t n_jobs, PkBases bases, const DpParams &P, uint32_t *counter, uint8_t *slab, uint32_t n_chunks,
+                     DpRes *res, uint32_t *pool, unsigned long long *cursor, unsigned long long pool_cap, hipStream_t st);
+bool lanes_eligible(const DpJob &j, int nt);
+size_t lanes_cig_bytes(int q_cap, int t_cap);
+size_t lanes_chunk_bytes(int nt);
+void launch_extd2_lanes(int nt, unsigned n_blocks, int q_cap, int t_cap, const DpJob *jobs, uint32_t n_jobs, PkBases bases, const DpParams &P, uint32_t *counter, uint8_t *slab, uint32_t n_chunks,
+                        DpRes *res, uint32_t *pool, unsigned long long *cursor, unsigned long long pool_cap, hipStream_t st);
 
 } // namespace pga

@@ -16,7 +16,7 @@
 //   * exact-max diagonals reduce (H,t) with the reference's 4-lane-strided tie order encoded in the key.
 // Persistent launch: a fixed grid of waves pulls problems from an atomic queue (problem sizes are ragged).
 #include "pga_common.h"
-#include "pga_dp.h"
+#include "pga_ksw_shared.h"
 #include <atomic>
 #include <chrono>
 #include <mutex>
@@ -26,53 +26,6 @@
 #include <cstring>
 
 namespace pga {
-
-#define KSW_NEG_INF (-0x40000000)
-#define EZ_RIGHT      0x02
-#define EZ_APPROX_MAX 0x08
-#define EZ_APPROX_DROP 0x10
-#define EZ_EXTZ_ONLY  0x40
-#define EZ_REV_CIGAR  0x80
-
-__device__ __forceinline__ int sx8(int v) { return __builtin_amdgcn_sbfe(v, 0, 8); }
-
-struct SeqView {
-	PkBases nt; uint64_t t_base, q_base;   // the packed store; target window start / query sequence start in it
-	int32_t qlen_full, qs, qlen, tlen;
-	bool q_rev, seq_rev;
-	__device__ __forceinline__ int target(int i) const { // 0 beyond the window (the reference's zero padding)
-		if (i >= tlen) return 0;
-		return nt.at(t_base + (uint64_t)(seq_rev ? tlen - 1 - i : i));
-	}
-	__device__ __forceinline__ int query(int j) const {
-		if (j < 0 || j >= qlen) return 0;
-		int pj = qs + (seq_rev ? qlen - 1 - j : j);
-		if (!q_rev) return nt.at(q_base + (uint64_t)(pj));
-		int c = nt.at(q_base + (uint64_t)(qlen_full - 1 - pj));
-		return c < 4 ? 3 - c : 4;
-	}
-};
-
-__device__ __forceinline__ void diag_range(int r, int qlen, int tlen, int w, int &st0, int &en0)
-{
-	int st = 0, en = tlen - 1;
-	if (st < r - qlen + 1) st = r - qlen + 1;
-	if (en > r) en = r;
-	if (st < (r - w + 1) >> 1) st = (r - w + 1) >> 1;
-	if (en > (r + w) >> 1) en = (r + w) >> 1;
-	st0 = st, en0 = en;
-}
-
-__device__ __forceinline__ long long wave_max64(long long v)
-{
-#pragma unroll
-	for (int d = 32; d >= 1; d >>= 1) {
-		int lo = __shfl_xor((int)(v & 0xffffffffLL), d), hi = __shfl_xor((int)(v >> 32), d);
-		long long o = ((long long)hi << 32) | (unsigned int)lo;
-		v = o > v ? o : v;
-	}
-	return v;
-}
 
 #define LDS_T 2048   // problems with tlen16 <= LDS_T keep their rows in LDS
 
@@ -94,24 +47,17 @@ void k_extd2(const DpJob *__restrict__ jobs, uint32_t n_jobs, PkBases bases, DpP
 		__syncthreads();
 		if (jid >= n_jobs) break;
 		const DpJob J = jobs[jid];
-		SeqView V;
-		V.nt = bases, V.t_base = J.t_off, V.q_base = J.q_off, V.qlen_full = J.qlen_full, V.qs = J.qs, V.qlen = J.qlen, V.tlen = J.tlen;
-		V.q_rev = J.q_rev, V.seq_rev = J.seq_rev;
+		const SeqView V(bases, J);
 		const int qlen = J.qlen, tlen = J.tlen, flag = J.flag, zdrop = J.zdrop, end_bonus = J.end_bonus;
 		int w = J.w;
-		int q = P.q, e = P.e, q2 = P.q2, e2 = P.e2;
-		const int qe_h = q + e;                                   // ksw2_extd2_sse.c:73 (taken before the swap)
-		if (q2 + e2 < q + e) { int t = q; q = q2, q2 = t, t = e, e = e2, e2 = t; }
-		const int qe = q + e, qe2 = q2 + e2;
-		const int sc_mch = P.sc_mch, sc_mis = P.sc_mis, sc_N = P.sc_ambi == 0 ? -e2 : P.sc_ambi;
+		const GapCosts G(P);
+		const int q = G.q, e = G.e, q2 = G.q2, e2 = G.e2, qe_h = G.qe_h, qe = G.qe, qe2 = G.qe2;
+		const int sc_mch = P.sc_mch, sc_mis = P.sc_mis, sc_N = G.sc_N;
 		const bool approx_max = flag & EZ_APPROX_MAX, right = flag & EZ_RIGHT;
 		if (w < 0) w = tlen > qlen ? tlen : qlen;
 		const int tlen16 = (tlen + 15) / 16 * 16;
 		int n_col = qlen < tlen ? qlen : tlen;
 		n_col = (((n_col < w + 1 ? n_col : w + 1) + 15) / 16 + 1) * 16;
-		int long_thres = e != e2 ? (q2 - q) / (e - e2) - 1 : 0;
-		if (q2 + e2 + long_thres * e2 > q + e + long_thres * e) ++long_thres;
-		const int long_diff = long_thres * (e - e2) - (q2 - q) - e2;
 
 		// row storage: LDS when it fits, else the head of this wave's HBM slab; the direction matrix follows
 		int8_t *rows; int32_t *H; uint8_t *pmat;
@@ -144,11 +90,11 @@ void k_extd2(const DpJob *__restrict__ jobs, uint32_t n_jobs, PkBases bases, DpP
 				else x1 = sx8(-q - e), x21 = sx8(-q2 - e2), v1 = sx8(-q - e);
 			} else {
 				x1 = sx8(-q - e), x21 = sx8(-q2 - e2);
-				v1 = r == 0 ? sx8(-q - e) : r < long_thres ? sx8(-e) : r == long_thres ? sx8(long_diff) : sx8(-e2);
+				v1 = sx8(G.first_row(r));
 			}
 			if (en >= r && lane == 0) {
 				y[r] = (int8_t)(-q - e), y2[r] = (int8_t)(-q2 - e2);
-				u[r] = (int8_t)(r == 0 ? -q - e : r < long_thres ? -e : r == long_thres ? long_diff : -e2);
+				u[r] = (int8_t)G.first_row(r);
 			}
 			// score profile, refreshed in 16-lane groups starting at st0 (ksw2_extd2_sse.c:165-181)
 			{
@@ -301,9 +247,7 @@ void k_extd2(const DpJob *__restrict__ jobs, uint32_t n_jobs, PkBases bases, DpP
 			if (j >= 0) push(1, (uint32_t)(j + 1));
 		}
 		n_cigar = __shfl(n_cigar, 0);
-		unsigned long long base = 0;
-		if (lane == 0 && n_cigar > 0) base = atomicAdd(pool_cursor, (unsigned long long)n_cigar);
-		base = ((unsigned long long)(unsigned)__shfl((int)(base >> 32), 0) << 32) | (unsigned)__shfl((int)(base & 0xffffffffULL), 0);
+		const unsigned long long base = cigar_reserve(lane == 0 && n_cigar > 0, 0, n_cigar, pool_cursor);
 		__builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
 		__syncthreads();
 		const bool rev_cigar = flag & EZ_REV_CIGAR;
@@ -332,13 +276,6 @@ size_t dp_slab_bytes(int qlen, int tlen, int w)
 	return (b + 255) & ~(size_t)255;
 }
 
-void launch_extd2_fast(int C, unsigned n_waves, const DpJob *jobs, uint32_t n_jobs, PkBases bases, const DpParams &P, uint32_t *counter, uint8_t *slab, size_t slab_bytes,
-                       DpRes *res, uint32_t *pool, unsigned long long *cursor, unsigned long long pool_cap, hipStream_t st);
-
-size_t wide_lds_bytes(int r_cap, int seq_cap, bool exact);
-void launch_extd2_wide(unsigned n_blocks, int n_threads, int r_cap, int seq_cap, bool exact, const DpJob *jobs, uint32_t n_jobs, PkBases bases, const DpParams &P, uint32_t *counter, uint8_t *slab, size_t slab_bytes,
-                       DpRes *res, uint32_t *pool, unsigned long long *cursor, unsigned long long pool_cap, hipStream_t st);
-
 // Problem classes (each is one persistent launch):
 //   0,1    register-resident kernel (pga_ksw_fast.hip), target <= 256 / <= 512 lanes, band never binding
 //   2,3,4  workgroup kernel (pga_ksw_wide.hip) by LDS footprint of the band ring + sequences: <= 48 KB (three workgroups
@@ -354,7 +291,6 @@ void launch_extd2_wide(unsigned n_blocks, int n_threads, int r_cap, int seq_cap,
 //   7      like 4, but exact-maximum problems (14 instead of 10 B of LDS per column: launched apart so that the approximate
 //          first passes of class 4 keep room for their sequences in LDS)
 #define DP_NCLASS 14
-#define WIDE_LDS_MAX (152 * 1024)
 static inline int wide_ring(const DpJob &j)
 {
 	const int T = (j.tlen + 15) / 16 * 16;
@@ -363,53 +299,6 @@ static inline int wide_ring(const DpJob &j)
 	return R > T ? T : R;
 }
 static inline int wide_seqcap(const DpJob &j) { return ((j.qlen > j.tlen ? j.qlen : j.tlen) + 15) / 16 * 16; }
-size_t ll_lds_bytes(int t_cap);
-size_t ll_multi_scratch_bytes();
-int ll_groups(uint32_t n_jobs, int t_max);
-void launch_ll_multi(int G, int t_cap, const DpJob *jobs, uint32_t n_jobs, PkBases bases, const DpParams &P, unsigned long long *scratch, DpRes *res, hipStream_t st);
-void launch_ll_i16(unsigned n_blocks, int t_cap, const DpJob *jobs, uint32_t n_jobs, PkBases bases, const DpParams &P, uint32_t *counter,
-                   unsigned long long *rowkey, size_t rowkey_stride, DpRes *res, hipStream_t st);
-
-#define BAND_MAXLEN 1024
-size_t band_slab_bytes(int max_diag);
-void launch_gapfill_band(unsigned n_waves, const DpJob *jobs, uint32_t n_jobs, PkBases bases, const DpParams &P, uint32_t *counter, uint8_t *slab, size_t slab_bytes,
-                         DpRes *res, uint32_t *pool, unsigned long long *cursor, unsigned long long pool_cap, hipStream_t st);
-
-bool strips_eligible(const DpJob &j, const DpParams &P);
-size_t strips_slab_bytes(const DpJob &j);
-int strips_count(const DpJob &j);
-size_t strips_bnd_words(const DpJob &j);
-void launch_approx_strips(unsigned n_blocks, const DpJob *jobs, const uint32_t *blk_job, const uint32_t *blk_strip, PkBases bases, const DpParams &P, uint8_t *slab, const uint64_t *slab_off,
-                          uint32_t *bnd, const uint64_t *bnd_off, uint32_t *done_ctr, DpRes *res, uint32_t *pool, unsigned long long *cursor, unsigned long long pool_cap, hipStream_t st);
-
-bool wstrips_on();
-bool wstrips_eligible(const DpJob &j, const DpParams &P);
-int wstrips_count(const DpJob &j);
-size_t wstrips_bnd_words(const DpJob &j);
-void launch_wstrips(unsigned n_blocks, const DpJob *jobs, const uint32_t *blk_job, const uint32_t *blk_strip, PkBases bases, const DpParams &P, uint8_t *slab, const uint64_t *slab_off,
-                    unsigned long long *bnd, const uint64_t *bnd_off, uint32_t *done_ctr, DpRes *res, uint32_t *pool, unsigned long long *cursor, unsigned long long pool_cap, hipStream_t st);
-int bstrips_mode();
-int bstrips_max_problems();
-int bstrips_long_diagonals();
-bool bstrips_eligible(const DpJob &j, const DpParams &P);
-size_t bstrips_slab_bytes(const DpJob &j);
-size_t bstrips_words(const DpJob &j);
-uint32_t bstrips_table(const DpJob &j, std::vector<uint32_t> &tab, size_t *words);
-void launch_bstrips(unsigned n_blocks, const DpJob *jobs, const uint32_t *blk_job, PkBases bases, const DpParams &P, uint8_t *slab, const uint64_t *slab_off,
-                    unsigned long long *bnd, const uint64_t *bnd_off, const uint32_t *tab, const uint64_t *tab_off, DpRes *res, uint32_t *pool, unsigned long long *cursor,
-                    unsigned long long pool_cap, hipStream_t st);
-bool pipe_eligible(const DpJob &j);
-int pipe_mode();
-size_t pipe_cig_bytes(int q_cap, int t_cap);
-size_t pipe_chunk_bytes();
-int pipe_max_chunks();
-void launch_ext_pipe(unsigned n_blocks, int q_cap, int t_cap, const DpJob *jobs, uint32_t n_jobs, PkBases bases, const DpParams &P, uint32_t *counter, uint8_t *slab, uint32_t n_chunks,
-                     DpRes *res, uint32_t *pool, unsigned long long *cursor, unsigned long long pool_cap, hipStream_t st);
-bool lanes_eligible(const DpJob &j, int nt);
-size_t lanes_cig_bytes(int q_cap, int t_cap);
-size_t lanes_chunk_bytes(int nt);
-void launch_extd2_lanes(int nt, unsigned n_blocks, int q_cap, int t_cap, const DpJob *jobs, uint32_t n_jobs, PkBases bases, const DpParams &P, uint32_t *counter, uint8_t *slab, uint32_t n_chunks,
-                        DpRes *res, uint32_t *pool, unsigned long long *cursor, unsigned long long pool_cap, hipStream_t st);
 
 static int dp_class(const DpJob &j, bool allow_band, const DpParams &P)
 {

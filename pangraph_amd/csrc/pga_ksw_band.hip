@@ -20,16 +20,13 @@
 // the wave's slab slice (32 coalesced bytes per problem and diagonal) and come back through 64-row LDS windows for the
 // backtrack, which the two groups walk side by side on lanes 0 and 32.
 #include "pga_common.h"
-#include "pga_dp.h"
-#include "pga_wave.h"
+#include "pga_ksw_shared.h"
 
 namespace pga {
 
 #define BAND_NEG (-(1 << 28))
-#define BAND_MAXLEN 1024           // longest query / target taken (LDS sequence buffers)
 #define BAND_ROWS 64               // backtrack window: diagonals per refill
 #define BAND_MAXCIG 248            // CIGAR operations kept in LDS; a problem with more goes through the full kernel
-#define EZ_APPROX_MAX 0x08
 
 // lane l <- lane l+1 (wave_shl:1); the last lane keeps `last`
 __device__ __forceinline__ int32_t wave_shl1(int32_t v, int32_t last) { return __builtin_amdgcn_update_dpp(last, v, 0x130, 0xf, 0xf, false); }
@@ -61,14 +58,9 @@ void k_gapfill_band(const DpJob *__restrict__ jobs, uint32_t n_jobs, PkBases bas
 		const int qlen = on ? J.qlen : 0, tlen = on ? J.tlen : 0;
 		// sequences into LDS (orientation resolved here)
 		{
-			const uint64_t t_base = J.t_off, q_base = J.q_off;          // base positions in the packed store
-			for (int i = gl; i < tlen; i += 32) s_t[g][i] = bases.at(t_base + (uint64_t)(J.seq_rev ? tlen - 1 - i : i));
-			for (int jx = gl; jx < qlen; jx += 32) {
-				const int pj = J.qs + (J.seq_rev ? qlen - 1 - jx : jx);
-				int c;
-				if (!J.q_rev) c = bases.at(q_base + (uint64_t)(pj)); else { c = bases.at(q_base + (uint64_t)(J.qlen_full - 1 - pj)); c = c < 4 ? 3 - c : 4; }
-				s_q[g][jx] = (uint8_t)c;
-			}
+			const SeqView SV(bases, J);
+			for (int i = gl; i < tlen; i += 32) s_t[g][i] = SV.target_in(i);
+			for (int jx = gl; jx < qlen; jx += 32) s_q[g][jx] = (uint8_t)SV.query_in(jx);
 		}
 		__builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
 		const int delta = tlen - qlen;
@@ -209,15 +201,13 @@ void k_gapfill_band(const DpJob *__restrict__ jobs, uint32_t n_jobs, PkBases bas
 			if (n_cigar < 0) ok = false;
 		}
 		__builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
-		unsigned long long base = 0;
-		if (gl == 0 && ok && n_cigar > 0) base = atomicAdd(pool_cursor, (unsigned long long)n_cigar);
-		base = ((unsigned long long)(unsigned)__shfl((int)(base >> 32), 32 * g) << 32) | (unsigned)__shfl((int)(base & 0xffffffffULL), 32 * g);
+		const unsigned long long base = cigar_reserve(gl == 0 && ok && n_cigar > 0, 32 * g, n_cigar, pool_cursor);   // one reservation per group
 		if (ok && n_cigar > 0 && base + (unsigned long long)n_cigar <= pool_cap)
 			for (int k = gl; k < n_cigar; k += 32) cigar_pool[base + k] = s_cig[g][n_cigar - 1 - k];
 		if (gl == 0 && on) {
 			DpRes R;
-			R.max = 0, R.max_q = -1, R.max_t = -1, R.mqe = -0x40000000, R.mqe_t = -1, R.mte = -0x40000000, R.mte_q = -1;
-			R.score = ok ? score : -0x40000000; R.zdropped = 0, R.reach_end = 0;
+			R.max = 0, R.max_q = -1, R.max_t = -1, R.mqe = KSW_NEG_INF, R.mqe_t = -1, R.mte = KSW_NEG_INF, R.mte_q = -1;
+			R.score = ok ? score : KSW_NEG_INF; R.zdropped = 0, R.reach_end = 0;
 			R.n_cigar = ok ? n_cigar : -9;                       // -9: not proven inside the corridor, run the full matrix
 			R.pad = 0, R.cigar_off = base;
 			res[jid] = R;

@@ -30,34 +30,17 @@
 // The evaluator then walks the path back (ksw2.h:127-159) through a 64 x 64 LDS window.  A clamped maximum hands the problem
 // back (n_cigar = -9: the workgroup kernel redoes it).  Parity: tests/test_gpu_parity.py (PGA_BSTRIPS=force sends every eligible problem here).
 #include "pga_common.h"
-#include "pga_dp.h"
-#include "pga_wave.h"
+#include "pga_ksw_shared.h"
 #include <cstring>
 #include <vector>
 
 namespace pga {
 
-#define KSW_NEG_INF (-0x40000000)
 #define BS_W 64
-#define BS_BT 64
-#define EZ_RIGHT      0x02
-#define EZ_APPROX_MAX 0x08
-#define EZ_EXTZ_ONLY  0x40
-#define EZ_REV_CIGAR  0x80
 
 struct BsCtl { uint32_t next_strip, stop, roles, pad[5]; };      // one per problem, zeroed before the launch
 static_assert(sizeof(BsCtl) == 32, "control block: four 64-bit words");
 
-__host__ __device__ __forceinline__ void bs_range(int r, int qlen, int tlen, int w, int &st0, int &en0)
-{
-	int st = 0, en = tlen - 1;
-	if (st < r - qlen + 1) st = r - qlen + 1;
-	if (en > r) en = r;
-	if (st < (r - w + 1) >> 1) st = (r - w + 1) >> 1;
-	if (en > (r + w) >> 1) en = (r + w) >> 1;
-	st0 = st, en0 = en;
-}
-__device__ __forceinline__ int bs_sx8(int v) { return __builtin_amdgcn_sbfe(v, 0, 8); }
 __device__ __forceinline__ int bs_byte(uint32_t v, int sh) { return __builtin_amdgcn_sbfe((int)v, sh, 8); }
 
 // the layout of a problem's words (64 bit each) behind bnd_off: control block | best key per diagonal | H[en0] per diagonal, H[st0] per diagonal
@@ -93,18 +76,13 @@ __device__ __forceinline__ void bstrip_body(const DpJob &J, const uint32_t jl, u
                DpRes *__restrict__ res, uint32_t *__restrict__ cigar_pool, unsigned long long *__restrict__ pool_cursor, unsigned long long pool_cap)
 {
 	const int lane = threadIdx.x;
-	const uint64_t t_base = J.t_off, q_base = J.q_off;
+	const SeqView SV(bases, J);
 	const int qlen = J.qlen, tlen = J.tlen, flag = J.flag, zdrop = J.zdrop, end_bonus = J.end_bonus;
 	int w = J.w;
 	if (w < 0) w = tlen > qlen ? tlen : qlen;
-	int q = P.q, e = P.e, q2 = P.q2, e2 = P.e2;
-	const int qe_h = q + e;
-	if (q2 + e2 < q + e) { int t = q; q = q2, q2 = t, t = e, e = e2, e2 = t; }
-	const int qe = q + e, qe2 = q2 + e2;
-	const int sc_mch = P.sc_mch, sc_mis = P.sc_mis, sc_N = P.sc_ambi == 0 ? -e2 : P.sc_ambi;
-	int long_thres = e != e2 ? (q2 - q) / (e - e2) - 1 : 0;
-	if (q2 + e2 + long_thres * e2 > q + e + long_thres * e) ++long_thres;
-	const int long_diff = long_thres * (e - e2) - (q2 - q) - e2;
+	const GapCosts G(P);
+	const int q = G.q, e = G.e, q2 = G.q2, e2 = G.e2, qe_h = G.qe_h, qe = G.qe, qe2 = G.qe2;
+	const int sc_mch = P.sc_mch, sc_mis = P.sc_mis, sc_N = G.sc_N;
 	const BsLayout Lo = bs_layout(qlen, tlen, J.w);
 	const int T = Lo.T, n_strips = Lo.n_strips, n_diag = Lo.n_diag, n_col = Lo.n_col;
 	uint8_t *pmat = slab_all + slab_off[jl];
@@ -119,17 +97,9 @@ __device__ __forceinline__ void bstrip_body(const DpJob &J, const uint32_t jl, u
 	const uint32_t *strip_r = tab + 2, *need = tab + 2 + 3 * (size_t)n_strips;
 	const int nblk_eff = (n_eff + 63) / 64;
 	uint32_t *s_key = (uint32_t*)s_win;
-	const int INI1 = bs_sx8(-q - e), INI2 = bs_sx8(-q2 - e2);
+	const int INI1 = sx8(-q - e), INI2 = sx8(-q2 - e2);
 	const uint32_t PK_INI = ((uint32_t)INI1 & 0xffu) | ((uint32_t)INI1 & 0xffu) << 8 | ((uint32_t)INI2 & 0xffu) << 16;
-	auto target_at = [&](int i) -> int { return (i >= 0 && i < tlen) ? (int)bases.at(t_base + (uint64_t)(J.seq_rev ? tlen - 1 - i : i)) : 0; };
-	auto query_at = [&](int j) -> int {
-		if (j < 0 || j >= qlen) return 0;
-		const int pj = J.qs + (J.seq_rev ? qlen - 1 - j : j);
-		if (!J.q_rev) return bases.at(q_base + (uint64_t)(pj));
-		const int c = bases.at(q_base + (uint64_t)(J.qlen_full - 1 - pj));
-		return c < 4 ? 3 - c : 4;
-	};
-	auto first_row = [&](int r) -> int { return bs_sx8(r == 0 ? -q - e : r < long_thres ? -e : r == long_thres ? long_diff : -e2); };
+	auto first_row = [&](int r) -> int { return sx8(G.first_row(r)); };
 	auto stopped = [&]() -> uint32_t { return __hip_atomic_load(&ctl->stop, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); };
 
 	// ---- roles: the first wave of the pool to arrive is the problem's EVALUATOR, the others take strips ----
@@ -158,7 +128,7 @@ __device__ __forceinline__ void bstrip_body(const DpJob &J, const uint32_t jl, u
 			const int mH = __builtin_amdgcn_readlane(mH_l, ii), mt = __builtin_amdgcn_readlane(mt_l, ii);
 			const int he = __builtin_amdgcn_readlane(hen, ii), hs = __builtin_amdgcn_readlane(hst, ii);
 			sat |= __builtin_amdgcn_readlane(sat_l, ii);
-			int st0, en0; bs_range(rr, qlen, tlen, w, st0, en0);
+			int st0, en0; diag_range(rr, qlen, tlen, w, st0, en0);
 			r_done = rr + 1;
 			if (en0 == tlen - 1) { if (he > ez_mte) ez_mte = he, ez_mte_q = rr - en0; if (rr == n_diag - 1) ez_score = he; }
 			if (rr - st0 == qlen - 1 && hs > ez_mqe) ez_mqe = hs, ez_mqe_t = st0;
@@ -189,27 +159,27 @@ __device__ __forceinline__ void bstrip_body(const DpJob &J, const uint32_t jl, u
 		const unsigned long long *bnd_in = k > 0 && rf_left <= rl_left ? bnd + (size_t)strip_r[3 * k - 1] - rf_left : nullptr;
 		unsigned long long *bnd_out = (int)k + 1 < n_strips ? bnd + (size_t)strip_r[3 * k + 2] - r_first : nullptr;
 		const int c0 = (int)k * BS_W, t = c0 + lane;
-		const int tb = target_at(t);
+		const int tb = SV.target_any(t);
 		// the lane's column: the rows at index t as the reference's freshly initialised arrays hold them (ksw2_extd2_sse.c:109-118)
 		int U = INI1, Y = INI1, Y2 = INI2, S = 0, H = KSW_NEG_INF;
 		uint32_t PK = PK_INI;
-		int qb = query_at(r_first - 1 - t);                         // query[(r - 1) - t] for r = r_first: what the slide below starts from
+		int qb = SV.query(r_first - 1 - t);                         // query[(r - 1) - t] for r = r_first: what the slide below starts from
 		bool gone = false;
 #ifdef PGA_BS_PROF
 		long long pf_poll = 0, pf_comp = 0, pf_blk = 0, pf_n = 0; const long long pf_t0 = clock64();
 #endif
 		// ranges of the diagonal before the strip's first (what column st's edge rule looks at, ksw2_extd2_sse.c:176-183)
 		int last_st = -1, last_en = -1;
-		if (r_first > 0) { int a0, a1; bs_range(r_first - 1, qlen, tlen, w, a0, a1); last_st = a0 & ~15, last_en = ((a1 + 16) & ~15) - 1; }
+		if (r_first > 0) { int a0, a1; diag_range(r_first - 1, qlen, tlen, w, a0, a1); last_st = a0 & ~15, last_en = ((a1 + 16) & ~15) - 1; }
 		for (int b = r_first >> 6; b <= r_last >> 6 && !gone; ++b) {
 			if (stopped()) { gone = true; break; }
 			const int r_lo = b * 64 > r_first ? b * 64 : r_first, r_hi = b * 64 + 63 < r_last ? b * 64 + 63 : r_last;
 			// what a diagonal needs that does not depend on the column, a diagonal per lane: its range, the first-row value, the query base that
 			// enters lane 0 (the loop below takes them by v_readlane: a dozen scalar instructions per diagonal less)
 			int v_st0, v_en0;
-			bs_range(b * 64 + lane, qlen, tlen, w, v_st0, v_en0);
+			diag_range(b * 64 + lane, qlen, tlen, w, v_st0, v_en0);
 			const int v_fr = first_row(b * 64 + lane);
-			const int qwin = query_at(b * 64 + lane - c0);
+			const int qwin = SV.query(b * 64 + lane - c0);
 			unsigned long long inw = (unsigned long long)(uint32_t)KSW_NEG_INF << 32 | PK_INI;
 			unsigned long long outw = 0;
 			int hen_acc = 0, hst_acc = 0; bool hen_set = false, hst_set = false;
@@ -257,12 +227,12 @@ __device__ __forceinline__ void bstrip_body(const DpJob &J, const uint32_t jl, u
 					{
 						int sc = tb == qb ? sc_mch : sc_mis;
 						sc = ((tb | qb) & 4) ? sc_N : sc;
-						S = (t >= st0 && t < st0 + span && t < T) ? bs_sx8(sc) : S;
+						S = (t >= st0 && t < st0 + span && t < T) ? sx8(sc) : S;
 					}
 					const bool in_rng = t >= st && t <= en;
 					const int xt1 = bs_byte(lw, 0), vt1 = bs_byte(lw, 8), x2t1 = bs_byte(lw, 16);
 					int z = S;
-					int a = bs_sx8(xt1 + vt1), bb = bs_sx8(Y + U), a2 = bs_sx8(x2t1 + vt1), b2 = bs_sx8(Y2 + U), d;
+					int a = sx8(xt1 + vt1), bb = sx8(Y + U), a2 = sx8(x2t1 + vt1), b2 = sx8(Y2 + U), d;
 					if (!RIGHT) {
 						d = a > z ? 1 : 0; z = a > z ? a : z;
 						d = bb > z ? 2 : d; z = bb > z ? bb : z;
@@ -275,20 +245,20 @@ __device__ __forceinline__ void bstrip_body(const DpJob &J, const uint32_t jl, u
 						d = z > b2 ? d : 4; z = z > b2 ? z : b2;
 					}
 					z = sc_mch < z ? sc_mch : z;
-					const int un = bs_sx8(z - vt1), vn = bs_sx8(z - U);
-					int tmp = bs_sx8(z - q); a = bs_sx8(a - tmp); bb = bs_sx8(bb - tmp);
-					tmp = bs_sx8(z - q2); a2 = bs_sx8(a2 - tmp); b2 = bs_sx8(b2 - tmp);
+					const int un = sx8(z - vt1), vn = sx8(z - U);
+					int tmp = sx8(z - q); a = sx8(a - tmp); bb = sx8(bb - tmp);
+					tmp = sx8(z - q2); a2 = sx8(a2 - tmp); b2 = sx8(b2 - tmp);
 					int xn, yn, x2n, y2n;
 					if (!RIGHT) {
-						xn = bs_sx8((a > 0 ? a : 0) - qe);     d |= a > 0 ? 0x08 : 0;
-						yn = bs_sx8((bb > 0 ? bb : 0) - qe);   d |= bb > 0 ? 0x10 : 0;
-						x2n = bs_sx8((a2 > 0 ? a2 : 0) - qe2); d |= a2 > 0 ? 0x20 : 0;
-						y2n = bs_sx8((b2 > 0 ? b2 : 0) - qe2); d |= b2 > 0 ? 0x40 : 0;
+						xn = sx8((a > 0 ? a : 0) - qe);     d |= a > 0 ? 0x08 : 0;
+						yn = sx8((bb > 0 ? bb : 0) - qe);   d |= bb > 0 ? 0x10 : 0;
+						x2n = sx8((a2 > 0 ? a2 : 0) - qe2); d |= a2 > 0 ? 0x20 : 0;
+						y2n = sx8((b2 > 0 ? b2 : 0) - qe2); d |= b2 > 0 ? 0x40 : 0;
 					} else {
-						xn = bs_sx8((0 > a ? 0 : a) - qe);     d |= !(0 > a) ? 0x08 : 0;
-						yn = bs_sx8((0 > bb ? 0 : bb) - qe);   d |= !(0 > bb) ? 0x10 : 0;
-						x2n = bs_sx8((0 > a2 ? 0 : a2) - qe2); d |= !(0 > a2) ? 0x20 : 0;
-						y2n = bs_sx8((0 > b2 ? 0 : b2) - qe2); d |= !(0 > b2) ? 0x40 : 0;
+						xn = sx8((0 > a ? 0 : a) - qe);     d |= !(0 > a) ? 0x08 : 0;
+						yn = sx8((0 > bb ? 0 : bb) - qe);   d |= !(0 > bb) ? 0x10 : 0;
+						x2n = sx8((0 > a2 ? 0 : a2) - qe2); d |= !(0 > a2) ? 0x20 : 0;
+						y2n = sx8((0 > b2 ? 0 : b2) - qe2); d |= !(0 > b2) ? 0x40 : 0;
 					}
 					// a column outside [st, en] keeps its rows; Un / Vn: what u[t], v[t] hold behind this diagonal
 					const int Un = in_rng ? un : U, Vn = in_rng ? vn : bs_byte(PK, 8);
@@ -369,80 +339,23 @@ __device__ __forceinline__ void bstrip_body(const DpJob &J, const uint32_t jl, u
 		if (lane == 0) __hip_atomic_store(&ctl->stop, 1u, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);      // strips that are still out there leave
 	}
 	int ez_reach_end = 0;
-	int n_cigar = 0, bi = -1, bj = -1;
+	int bi = -1, bj = -1;
 	if (sat) {}
 	else if (!ez_zdropped && !(flag & EZ_EXTZ_ONLY)) bi = tlen - 1, bj = qlen - 1;
 	else if (!ez_zdropped && (flag & EZ_EXTZ_ONLY) && ez_mqe + end_bonus > ez_max) ez_reach_end = 1, bi = ez_mqe_t, bj = qlen - 1;
 	else if (ez_max_t >= 0 && ez_max_q >= 0) bi = ez_max_t, bj = ez_max_q;
-	{
-		int i = bi, j = bj, state = 0; long long guard = 0;
-		uint32_t last_op = 0xffffffffu, run_len = 0;
-		auto cg_push = [&](uint32_t op, uint32_t len) {
-			if (op == last_op) { run_len += len; return; }
-			if (last_op != 0xffffffffu) { if (lane == 0) cig_tmp[n_cigar] = run_len << 4 | last_op; ++n_cigar; }
-			last_op = op; run_len = len;
-		};
-		auto cg_flush = [&] { if (last_op != 0xffffffffu && n_cigar >= 0) { if (lane == 0) cig_tmp[n_cigar] = run_len << 4 | last_op; ++n_cigar; last_op = 0xffffffffu; } };
-		while (i >= 0 && j >= 0) {
-			if (++guard > 4000000) { n_cigar = -7; break; }
-			const int r_hi = i + j, c_lo = i - (BS_BT - 1);
-			{
-				uint8_t wv[BS_BT];
-#pragma unroll
-				for (int row = 0; row < BS_BT; ++row) {
-					const int r = r_hi - row, col = c_lo + lane;
-					uint8_t val = 0;
-					if (r >= 0 && col >= 0) {
-						int st0, en0; bs_range(r, qlen, tlen, w, st0, en0);
-						const int off = st0 / 16 * 16, off_end = (en0 + 16) / 16 * 16 - 1;
-						if (st0 <= en0 && col >= off && col <= off_end) val = pmat[(size_t)r * n_col + (size_t)(col - off)];
-					}
-					wv[row] = val;
-				}
-#pragma unroll
-				for (int row = 0; row < BS_BT; ++row) s_win[row * BS_BT + lane] = wv[row];
-			}
-			__builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
-			while (i >= 0 && j >= 0) {
-				const int r = i + j, row = r_hi - r;
-				if (row >= BS_BT || i < c_lo) break;
-				int st0, en0; bs_range(r, qlen, tlen, w, st0, en0);
-				const int off = st0 / 16 * 16, off_end = (en0 + 16) / 16 * 16 - 1;
-				int force_state = -1;
-				if (i < off) force_state = 2;
-				if (i > off_end) force_state = 1;
-				const uint32_t tmp = force_state < 0 ? s_win[row * BS_BT + (i - c_lo)] : 0;
-				if (state == 0) state = tmp & 7;
-				else if (!(tmp >> (state + 2) & 1)) state = 0;
-				if (state == 0) state = tmp & 7;
-				if (force_state >= 0) state = force_state;
-				uint32_t op;
-				if (state == 0) op = 0, --i, --j;
-				else if (state == 1 || state == 3) op = 2, --i;
-				else op = 1, --j;
-				cg_push(op, 1u);
-			}
-			__builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
-		}
-		if (bi >= 0 && bj >= 0 && n_cigar >= 0) {
-			if (i >= 0) cg_push(2u, (uint32_t)(i + 1));
-			if (j >= 0) cg_push(1u, (uint32_t)(j + 1));
-		}
-		cg_flush();
-	}
+	long long guard = 0;
+	const int n_cigar = backtrack_windowed<BT_WIN, false>(lane, bi, bj, s_win, cig_tmp, guard, 4000000,
+		[&](int r, int &st0, int &en0) { diag_range(r, qlen, tlen, w, st0, en0); },
+		[&](int r, int col) -> uint8_t {                           // stored: the sixteen-rounded range
+			int st0, en0; diag_range(r, qlen, tlen, w, st0, en0);
+			const int off = st0 / 16 * 16, off_end = (en0 + 16) / 16 * 16 - 1;
+			return st0 <= en0 && col >= off && col <= off_end ? pmat[(size_t)r * n_col + (size_t)(col - off)] : (uint8_t)0;
+		});
 	__builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
-	unsigned long long base = 0;
-	if (lane == 0 && n_cigar > 0) base = atomicAdd(pool_cursor, (unsigned long long)n_cigar);
-	base = ((unsigned long long)(unsigned)__shfl((int)(base >> 32), 0) << 32) | (unsigned)__shfl((int)(base & 0xffffffffULL), 0);
-	const bool rev_cigar = flag & EZ_REV_CIGAR;
-	if (n_cigar > 0 && base + (unsigned long long)n_cigar <= pool_cap)
-		for (int c = lane; c < n_cigar; c += 64) cigar_pool[base + c] = rev_cigar ? cig_tmp[c] : cig_tmp[n_cigar - 1 - c];
-	if (lane == 0) {
-		DpRes R;
-		R.max = ez_max, R.max_q = ez_max_q, R.max_t = ez_max_t, R.mqe = ez_mqe, R.mqe_t = ez_mqe_t, R.mte = ez_mte, R.mte_q = ez_mte_q;
-		R.score = ez_score, R.zdropped = ez_zdropped, R.reach_end = ez_reach_end, R.n_cigar = sat ? -9 : n_cigar, R.pad = r_done, R.cigar_off = base;
-		res[jl] = R;
-	}
+	DpRes R = ez_record(ez_max, ez_max_q, ez_max_t, ez_mqe, ez_mqe_t, ez_mte, ez_mte_q, ez_score, ez_zdropped, ez_reach_end);
+	R.n_cigar = sat ? -9 : n_cigar, R.pad = r_done;
+	cigar_commit<false, true>(lane, n_cigar, flag & EZ_REV_CIGAR, cig_tmp, cigar_pool, pool_cursor, pool_cap, R, &res[jl]);
 }
 
 __global__ __launch_bounds__(64)
@@ -481,7 +394,6 @@ size_t bstrips_slab_bytes(const DpJob &j)
 	const BsLayout L = bs_layout(j.qlen, j.tlen, j.w);
 	return (((size_t)L.n_diag * L.n_col + 15) & ~(size_t)15) + 4 * ((size_t)j.qlen + j.tlen + 8) + 256;
 }
-uint32_t bstrips_table(const DpJob &j, std::vector<uint32_t> &tab, size_t *words);
 size_t bstrips_words(const DpJob &j) { std::vector<uint32_t> scratch; size_t w = 0; (void)bstrips_table(j, scratch, &w); return w; }
 // the problem's table (see k_bstrips) appended to `tab`; returns the number of waves in its pool, *words = 64-bit words of the problem's region
 uint32_t bstrips_table(const DpJob &j, std::vector<uint32_t> &tab, size_t *words)
@@ -491,7 +403,7 @@ uint32_t bstrips_table(const DpJob &j, std::vector<uint32_t> &tab, size_t *words
 	int n_eff = L.n_diag;
 	std::vector<int> st((size_t)L.n_diag), en((size_t)L.n_diag);
 	for (int r = 0; r < L.n_diag; ++r) {
-		int st0, en0; bs_range(r, j.qlen, j.tlen, w, st0, en0);
+		int st0, en0; diag_range(r, j.qlen, j.tlen, w, st0, en0);
 		if (st0 > en0) { n_eff = r; break; }
 		st[(size_t)r] = st0 & ~15; en[(size_t)r] = ((en0 + 16) & ~15) - 1;
 	}

@@ -16,31 +16,11 @@
 //   * direction bytes stream to the wave's HBM slab (64 coalesced bytes per chunk and diagonal); the backtrack
 //     pulls a 64-row x 128-column window around the path into LDS with coalesced loads and walks it there.
 #include "pga_common.h"
-#include "pga_dp.h"
-#include "pga_wave.h"
+#include "pga_ksw_shared.h"
 #include "pga_pk16.h"
 
 namespace pga {
 
-#define KSW_NEG_INF (-0x40000000)
-#define EZ_RIGHT      0x02
-#define EZ_APPROX_MAX 0x08
-#define EZ_EXTZ_ONLY  0x40
-#define EZ_REV_CIGAR  0x80
-
-__device__ __forceinline__ long long wave_max64f(long long v)
-{
-#pragma unroll
-	for (int d = 32; d >= 1; d >>= 1) {
-		int lo = __shfl_xor((int)(v & 0xffffffffLL), d), hi = __shfl_xor((int)(v >> 32), d);
-		long long o = ((long long)hi << 32) | (unsigned int)lo;
-		v = o > v ? o : v;
-	}
-	return v;
-}
-
-#define BT_ROWS 64
-#define BT_COLS 64
 
 template <int C>
 __global__ __launch_bounds__(64)
@@ -48,17 +28,12 @@ void k_extd2_fast(const DpJob *__restrict__ jobs, uint32_t n_jobs, PkBases bases
                   uint32_t *__restrict__ job_counter, uint8_t *__restrict__ slab_all, size_t slab_bytes,
                   DpRes *__restrict__ res, uint32_t *__restrict__ cigar_pool, unsigned long long *__restrict__ pool_cursor, unsigned long long pool_cap)
 {
-	__shared__ uint8_t s_win[BT_ROWS * BT_COLS];
+	__shared__ uint8_t s_win[BT_WIN * BT_WIN];
 	const int lane = threadIdx.x;
 	uint8_t *slab = slab_all + (size_t)blockIdx.x * slab_bytes;
-	int q = P.q, e = P.e, q2 = P.q2, e2 = P.e2;
-	const int qe_h = q + e;
-	if (q2 + e2 < q + e) { int t = q; q = q2, q2 = t, t = e, e = e2, e2 = t; }
-	const int qe = q + e, qe2 = q2 + e2;
-	const int sc_mch = P.sc_mch, sc_mis = P.sc_mis, sc_N = P.sc_ambi == 0 ? -e2 : P.sc_ambi;
-	int long_thres = e != e2 ? (q2 - q) / (e - e2) - 1 : 0;
-	if (q2 + e2 + long_thres * e2 > q + e + long_thres * e) ++long_thres;
-	const int long_diff = long_thres * (e - e2) - (q2 - q) - e2;
+	const GapCosts G(P);
+	const int q = G.q, e = G.e, q2 = G.q2, e2 = G.e2, qe_h = G.qe_h, qe = G.qe, qe2 = G.qe2;
+	const int sc_mch = P.sc_mch, sc_mis = P.sc_mis, sc_N = G.sc_N;
 
 	long long guard = 0;
 	for (;;) {
@@ -67,7 +42,7 @@ void k_extd2_fast(const DpJob *__restrict__ jobs, uint32_t n_jobs, PkBases bases
 		jid = (uint32_t)__shfl((int)jid, 0);
 		if (jid >= n_jobs) break;
 		const DpJob J = jobs[jid];
-		const uint64_t t_base = J.t_off, q_base = J.q_off;          // base positions in the packed store
+		const SeqView SV(bases, J);
 		const int qlen = J.qlen, tlen = J.tlen, flag = J.flag, zdrop = J.zdrop, end_bonus = J.end_bonus;
 		const bool approx_max = flag & EZ_APPROX_MAX, right = flag & EZ_RIGHT;
 		const int w = J.w;
@@ -76,20 +51,11 @@ void k_extd2_fast(const DpJob *__restrict__ jobs, uint32_t n_jobs, PkBases bases
 		uint8_t *pmat = slab;
 		uint32_t *cig_tmp = (uint32_t*)(pmat + (((size_t)(qlen + tlen - 1) * n_col + 15) & ~(size_t)15));
 
-		auto target_at = [&](int i) -> int { return i < tlen ? (int)bases.at(t_base + (uint64_t)(J.seq_rev ? tlen - 1 - i : i)) : 0; };
-		auto query_at = [&](int j) -> int {
-			if (j < 0 || j >= qlen) return 0;
-			int pj = J.qs + (J.seq_rev ? qlen - 1 - j : j);
-			if (!J.q_rev) return bases.at(q_base + (uint64_t)(pj));
-			int c = bases.at(q_base + (uint64_t)(J.qlen_full - 1 - pj));
-			return c < 4 ? 3 - c : 4;
-		};
-
 		int u[C], v[C], x[C], y[C], x2[C], y2[C], tb[C], qb[C], H[C];
 #pragma unroll
 		for (int c = 0; c < C; ++c) {
 			u[c] = v[c] = x[c] = y[c] = -q - e; x2[c] = y2[c] = -q2 - e2;
-			tb[c] = target_at(lane + 64 * c); qb[c] = 0; H[c] = KSW_NEG_INF;
+			tb[c] = SV.target(lane + 64 * c); qb[c] = 0; H[c] = KSW_NEG_INF;
 		}
 		// Gap fills between near-identical stretches, decided without the matrix: for two equally long sequences that differ
 		// in m positions (no ambiguous bases), every alignment other than the main diagonal has at least one insertion and one
@@ -102,7 +68,7 @@ void k_extd2_fast(const DpJob *__restrict__ jobs, uint32_t n_jobs, PkBases bases
 #pragma unroll
 			for (int c = 0; c < C; ++c) {
 				const int t = lane + 64 * c;
-				if (t < tlen) { const int qc = query_at(t); ambi |= qc > 3 || tb[c] > 3; n_mis += qc != tb[c]; }
+				if (t < tlen) { const int qc = SV.query(t); ambi |= qc > 3 || tb[c] > 3; n_mis += qc != tb[c]; }
 			}
 			const unsigned long long any_ambi = __ballot(ambi);
 			int m_tot = 0;                                                // sum over lanes (a lane holds at most C columns)
@@ -137,16 +103,17 @@ void k_extd2_fast(const DpJob *__restrict__ jobs, uint32_t n_jobs, PkBases bases
 				U[p] = V[p] = X[p] = Y[p] = splat2(-q - e); X2[p] = Y2[p] = splat2(-q2 - e2);
 				TB[p].x = (short)tb[2 * p]; TB[p].y = (short)tb[2 * p + 1]; QB[p] = splat2(0);
 			}
-			int qblock = query_at(lane);
+			int qblock = SV.query(lane);
 			{ const int q0 = __builtin_amdgcn_readlane(qblock, 0); if (lane == 0) QB[0].x = (short)q0; }
 			const s2_t ZERO = splat2(0), ONE = splat2(1), MCH = splat2(sc_mch), DMIS = splat2(sc_mis - sc_mch), SCN = splat2(sc_N), Q1 = splat2(q), Q2 = splat2(q2), QE = splat2(qe), QE2 = splat2(qe2);
 			const s2_t INIT1 = splat2(-q - e), INIT2 = splat2(-q2 - e2), EIGHT = splat2(8), C16 = splat2(16), C32 = splat2(32), C64 = splat2(64);
 			int H0 = 0, last_H0_t = 0;
 			const int n_diag = qlen + tlen - 1;
 			for (int r = 0; r < n_diag; ++r) {
-				const int st0 = r - qlen + 1 > 0 ? r - qlen + 1 : 0, en0 = r < tlen - 1 ? r : tlen - 1;
+				int st0, en0;
+				diag_range(r, qlen, tlen, st0, en0);
 				const int st = st0 & ~15;
-				const int bnd = r == 0 ? -q - e : r < long_thres ? -e : r == long_thres ? long_diff : -e2;
+				const int bnd = G.first_row(r);
 				const s2_t BND = splat2(bnd);
 				uint8_t *prow = pmat + (size_t)r * n_col - st;
 #pragma unroll
@@ -210,7 +177,7 @@ void k_extd2_fast(const DpJob *__restrict__ jobs, uint32_t n_jobs, PkBases bases
 				// query bases move one lane up for the next diagonal; lane 0 takes query[r+1]
 				{
 					const int nr = r + 1;
-					if ((nr & 63) == 0) qblock = query_at(nr + lane);
+					if ((nr & 63) == 0) qblock = SV.query(nr + lane);
 					const int qnew = rl(qblock, nr & 63);
 #pragma unroll
 					for (int p = NP - 1; p >= 0; --p) {
@@ -221,16 +188,17 @@ void k_extd2_fast(const DpJob *__restrict__ jobs, uint32_t n_jobs, PkBases bases
 				}
 			}
 		} else {
-		int qblock = query_at(lane);                 // query[0..63]
+		int qblock = SV.query(lane);                 // query[0..63]
 		qb[0] = lane == 0 ? __shfl(qblock, 0) : 0;   // diagonal 0: lane 0 needs query[0]
 
 		int H0 = 0, last_H0_t = 0;
 		const int n_diag = qlen + tlen - 1;
 
 		for (int r = 0; r < n_diag; ++r) {
-			const int st0 = r - qlen + 1 > 0 ? r - qlen + 1 : 0, en0 = r < tlen - 1 ? r : tlen - 1;
+			int st0, en0;
+			diag_range(r, qlen, tlen, st0, en0);
 			const int st = st0 & ~15;
-			const int bnd = r == 0 ? -q - e : r < long_thres ? -e : r == long_thres ? long_diff : -e2;   // first row / first column value
+			const int bnd = G.first_row(r);   // first row / first column value
 			uint8_t *prow = pmat + (size_t)r * n_col - st;
 #pragma unroll
 			for (int c = C - 1; c >= 0; --c) {
@@ -309,7 +277,7 @@ void k_extd2_fast(const DpJob *__restrict__ jobs, uint32_t n_jobs, PkBases bases
 						}
 						if (t == en0) H[c] = Hen;
 					}
-					best = wave_max64f(best);
+					best = wave_max64(best);
 					max_H = (int)(best >> 32);
 					const unsigned ord = 0xffffffffu - (unsigned)(best & 0xffffffffLL);
 					max_t = ord == 0 ? en0 : (int)((ord - 1) & 0x0fffffffu);
@@ -356,7 +324,7 @@ void k_extd2_fast(const DpJob *__restrict__ jobs, uint32_t n_jobs, PkBases bases
 			// query bases move one lane up for the next diagonal; lane 0 takes query[r+1]
 			{
 				const int nr = r + 1;
-				if ((nr & 63) == 0) qblock = query_at(nr + lane);
+				if ((nr & 63) == 0) qblock = SV.query(nr + lane);
 				const int qnew = rl(qblock, nr & 63);
 #pragma unroll
 				for (int c = C - 1; c >= 0; --c) {
@@ -369,84 +337,22 @@ void k_extd2_fast(const DpJob *__restrict__ jobs, uint32_t n_jobs, PkBases bases
 		}
 
 		// ---- backtrack (ksw2.h:127-159): lane 0 walks an LDS window refilled by the whole wave ----
-		int n_cigar = 0, bi = -1, bj = -1;
+		int bi = -1, bj = -1;
 		if (!ez_zdropped && !(flag & EZ_EXTZ_ONLY)) bi = tlen - 1, bj = qlen - 1;
 		else if (!ez_zdropped && (flag & EZ_EXTZ_ONLY) && ez_mqe + end_bonus > ez_max) ez_reach_end = 1, bi = ez_mqe_t, bj = qlen - 1;
 		else if (ez_max_t >= 0 && ez_max_q >= 0) bi = ez_max_t, bj = ez_max_q;
 		__builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");                  // direction bytes written by other lanes
-		{
-			int i = bi, j = bj, state = 0;
-			uint32_t last_op = 0xffffffffu;
-			uint32_t run_len = 0;                               // the operation being extended lives in registers: one store per operation, not a
-			auto cg_push = [&](uint32_t op, uint32_t len) {     // read-modify-write of device memory per path step
-				if (op == last_op) { run_len += len; return; }
-				if (last_op != 0xffffffffu) { if (lane == 0) cig_tmp[n_cigar] = run_len << 4 | last_op; ++n_cigar; }
-				last_op = op; run_len = len;
-			};
-			auto cg_flush = [&] { if (last_op != 0xffffffffu && n_cigar >= 0) { if (lane == 0) cig_tmp[n_cigar] = run_len << 4 | last_op; ++n_cigar; last_op = 0xffffffffu; } };
-			uint32_t *cig = cig_tmp;
-			while (i >= 0 && j >= 0) {                                          // wave-uniform loop: every lane tracks (i,j,state)
-				if (++guard > 1000000) { n_cigar = -7; break; }                  // safety net: a stuck wave would take the GPU down
-				// window: rows r_hi-63 .. r_hi, target columns i-63 .. i (the path moves at most one column per step)
-				const int r_hi = i + j, c_lo = i - (BT_COLS - 1);
-				{
-					// all rows of the window are requested before the first one is stored: 64 loads in flight instead of 64 round trips
-					uint8_t wv[BT_ROWS];
-#pragma unroll
-					for (int row = 0; row < BT_ROWS; ++row) {
-						const int r = r_hi - row, col = c_lo + lane;
-						uint8_t val = 0;
-						if (r >= 0 && col >= 0) {
-							const int st0 = r - qlen + 1 > 0 ? r - qlen + 1 : 0, en0 = r < tlen - 1 ? r : tlen - 1;
-							if (col >= st0 && col <= en0) val = pmat[(size_t)r * n_col + (col - (st0 & ~15))];
-						}
-						wv[row] = val;
-					}
-#pragma unroll
-					for (int row = 0; row < BT_ROWS; ++row) s_win[row * BT_COLS + lane] = wv[row];
-				}
-				__builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");   // single-wave block: LDS is in order, a fence replaces the barrier
-				// walk while the path stays inside the window
-				while (i >= 0 && j >= 0) {
-					const int r = i + j, row = r_hi - r;
-					if (row >= BT_ROWS || i < c_lo) break;
-					const int st0 = r - qlen + 1 > 0 ? r - qlen + 1 : 0, en0 = r < tlen - 1 ? r : tlen - 1;
-					const int off = st0 & ~15, off_end = ((en0 + 16) & ~15) - 1;
-					int force_state = -1;
-					if (i < off) force_state = 2;
-					if (i > off_end) force_state = 1;
-					const uint32_t tmp = force_state < 0 ? s_win[row * BT_COLS + (i - c_lo)] : 0;
-					if (state == 0) state = tmp & 7;
-					else if (!(tmp >> (state + 2) & 1)) state = 0;
-					if (state == 0) state = tmp & 7;
-					if (force_state >= 0) state = force_state;
-					uint32_t op;
-					if (state == 0) op = 0, --i, --j;
-					else if (state == 1 || state == 3) op = 2, --i;
-					else op = 1, --j;
-					cg_push(op, 1u);
-				}
-				__builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
-			}
-			if (bi >= 0 && bj >= 0) {
-				if (i >= 0) cg_push(2u, (uint32_t)(i + 1));
-				if (j >= 0) cg_push(1u, (uint32_t)(j + 1));
-			}
-			cg_flush();
-		}
-		unsigned long long base = 0;
-		if (lane == 0 && n_cigar > 0) base = atomicAdd(pool_cursor, (unsigned long long)n_cigar);
-		base = ((unsigned long long)(unsigned)__shfl((int)(base >> 32), 0) << 32) | (unsigned)__shfl((int)(base & 0xffffffffULL), 0);
-		__builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
-		const bool rev_cigar = flag & EZ_REV_CIGAR;
-		if (base + (unsigned long long)n_cigar <= pool_cap)
-			for (int c = lane; c < n_cigar; c += 64) cigar_pool[base + c] = rev_cigar ? cig_tmp[c] : cig_tmp[n_cigar - 1 - c];
-		if (lane == 0) {
-			DpRes R;
-			R.max = ez_max, R.max_q = ez_max_q, R.max_t = ez_max_t, R.mqe = ez_mqe, R.mqe_t = ez_mqe_t, R.mte = ez_mte, R.mte_q = ez_mte_q;
-			R.score = ez_score, R.zdropped = ez_zdropped, R.reach_end = ez_reach_end, R.n_cigar = n_cigar, R.pad = 0, R.cigar_off = base;
-			res[jid] = R;
-		}
+		// this class alone: the guard counts the windows of ALL problems of the wave and trips at a million, a tripped walk still pushes its
+		// leading gap, a cell counts as stored inside [st0, en0] proper, and the copy-out does not ask for n_cigar > 0
+		const int n_cigar = backtrack_windowed<BT_WIN, true>(lane, bi, bj, s_win, cig_tmp, guard, 1000000,
+			[&](int r, int &st0, int &en0) { diag_range(r, qlen, tlen, st0, en0); },
+			[&](int r, int col) -> uint8_t {
+				int st0, en0; diag_range(r, qlen, tlen, st0, en0);
+				return col >= st0 && col <= en0 ? pmat[(size_t)r * n_col + (col - (st0 & ~15))] : (uint8_t)0;
+			});
+		DpRes R = ez_record(ez_max, ez_max_q, ez_max_t, ez_mqe, ez_mqe_t, ez_mte, ez_mte_q, ez_score, ez_zdropped, ez_reach_end);
+		R.n_cigar = n_cigar, R.pad = 0;
+		cigar_commit<true, false>(lane, n_cigar, flag & EZ_REV_CIGAR, cig_tmp, cigar_pool, pool_cursor, pool_cap, R, &res[jid]);
 	}
 }
 

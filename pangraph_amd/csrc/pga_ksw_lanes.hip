@@ -20,47 +20,20 @@
 //     LDS only (direction bytes are fire-and-forget 8-byte stores, fenced before the backtrack).
 // Reference semantics, 16-lane rounding of the ranges, stale score bytes beyond the profile span and the traceback are the
 // ones of pga_ksw_wide.hip (see there and pga_ksw.hip); the parity suites of tests/test_gpu_parity.py run both.
-#include <mutex>
 #include "pga_common.h"
-#include "pga_dp.h"
-#include "pga_wave.h"
+#include "pga_ksw_shared.h"
 #include "pga_pk16.h"
 #include <cstdio>
 #include <type_traits>
 
 namespace pga {
 
-#define KSW_NEG_INF (-0x40000000)
-#define EZ_RIGHT      0x02
-#define EZ_APPROX_MAX 0x08
-#define EZ_APPROX_DROP 0x10
-#define EZ_EXTZ_ONLY  0x40
-#define EZ_REV_CIGAR  0x80
-#define LBT 64
 #define LANES_C 8
 #define LANES_CHUNK (2u << 20)     // bytes of a direction-matrix chunk
 #define LANES_CHUNK_NARROW (512u << 10)   // ... of the one-wave instantiation (rings of at most 512 columns)
 #define LANES_MAXCHUNK 192
 __host__ __device__ constexpr uint32_t lanes_chunk_of(int nt) { return nt <= 64 ? LANES_CHUNK_NARROW : LANES_CHUNK; }
 
-__device__ __forceinline__ void diag_range_l(int r, int qlen, int tlen, int w, int &st0, int &en0)
-{
-	int st = 0, en = tlen - 1;
-	if (st < r - qlen + 1) st = r - qlen + 1;
-	if (en > r) en = r;
-	if (st < (r - w + 1) >> 1) st = (r - w + 1) >> 1;
-	if (en > (r + w) >> 1) en = (r + w) >> 1;
-	st0 = st, en0 = en;
-}
-
-__device__ __forceinline__ int sx8l(int v) { return __builtin_amdgcn_sbfe(v, 0, 8); }
-// Packed 16-bit operations as the instructions themselves: written through the vector extensions, min(x, 1) * c and friends are
-// canonicalised into per-half compares and selects (three to five instructions where one v_pk_* does it).
-__device__ __forceinline__ s2_t k_max(s2_t a, s2_t b) { int r; asm("v_pk_max_i16 %0, %1, %2" : "=v"(r) : "v"(as_i(a)), "v"(as_i(b))); return as_s2(r); }
-__device__ __forceinline__ s2_t k_min(s2_t a, s2_t b) { int r; asm("v_pk_min_i16 %0, %1, %2" : "=v"(r) : "v"(as_i(a)), "v"(as_i(b))); return as_s2(r); }
-__device__ __forceinline__ s2_t k_minu(s2_t a, s2_t b) { int r; asm("v_pk_min_u16 %0, %1, %2" : "=v"(r) : "v"(as_i(a)), "v"(as_i(b))); return as_s2(r); }
-__device__ __forceinline__ s2_t k_mad(s2_t a, s2_t b, s2_t c) { int r; asm("v_pk_mad_u16 %0, %1, %2, %3" : "=v"(r) : "v"(as_i(a)), "v"(as_i(b)), "v"(as_i(c))); return as_s2(r); }
-__device__ __forceinline__ s2_t k_shr(s2_t sh, s2_t a) { int r; asm("v_pk_lshrrev_b16 %0, %1, %2" : "=v"(r) : "v"(as_i(sh)), "v"(as_i(a))); return as_s2(r); }
 
 struct __attribute__((aligned(16))) LaneRec {      // what a wave publishes per diagonal (two copies, by diagonal parity)
 	uint32_t key;             // best packed (H, tie order, column) key among its columns
@@ -81,7 +54,7 @@ void k_extd2_lanes(const DpJob *__restrict__ jobs, uint32_t n_jobs, PkBases base
 	__shared__ uint32_t s_job;
 	__shared__ LaneRec s_rec[2][NT / 64];
 	__shared__ int s_hen[2], s_hst[2], s_h0v[2], s_h0u[2];
-	__shared__ uint8_t s_win[LBT * LBT];
+	__shared__ uint8_t s_win[BT_WIN * BT_WIN];
 	const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
 	// scratch: one CIGAR buffer per workgroup, then the pool of direction-matrix CHUNKS.  A workgroup takes chunks as its diagonals
 	// need them (most extensions z-drop after ~1.5 k diagonals and touch 2 MB of a matrix that would reserve 30 MB) and keeps them
@@ -93,14 +66,9 @@ void k_extd2_lanes(const DpJob *__restrict__ jobs, uint32_t n_jobs, PkBases base
 	__shared__ uint32_t s_chunk[LANES_MAXCHUNK];
 	__shared__ int s_have;
 	if (threadIdx.x == 0) s_have = 0;
-	int q = P.q, e = P.e, q2 = P.q2, e2 = P.e2;
-	const int qe_h = q + e;
-	if (q2 + e2 < q + e) { int t = q; q = q2, q2 = t, t = e, e = e2, e2 = t; }
-	const int qe = q + e, qe2 = q2 + e2;
-	const int sc_mch = P.sc_mch, sc_mis = P.sc_mis, sc_N = P.sc_ambi == 0 ? -e2 : P.sc_ambi;
-	int long_thres = e != e2 ? (q2 - q) / (e - e2) - 1 : 0;
-	if (q2 + e2 + long_thres * e2 > q + e + long_thres * e) ++long_thres;
-	const int long_diff = long_thres * (e - e2) - (q2 - q) - e2;
+	const GapCosts G(P);
+	const int q = G.q, e = G.e, q2 = G.q2, e2 = G.e2, qe_h = G.qe_h, qe = G.qe, qe2 = G.qe2;
+	const int sc_mch = P.sc_mch, sc_mis = P.sc_mis, sc_N = G.sc_N;
 	const uint32_t sc_tab = (uint32_t)(uint8_t)sc_mch | (uint32_t)(uint8_t)sc_mis << 8 | (uint32_t)(uint8_t)sc_N << 16 | (uint32_t)(uint8_t)sc_N << 24;
 	const s2_t ZERO = splat2(0), ONE = splat2(1), FOUR = splat2(4), MCH = splat2(sc_mch << 8), Q1 = splat2(q << 8), Q2 = splat2(q2 << 8), QE = splat2(qe << 8), QE2 = splat2(qe2 << 8);
 	const s2_t C8 = splat2(8), C16 = splat2(16), C32 = splat2(32), C64 = splat2(64), C120 = splat2(120), C15 = splat2(15), CM8 = splat2(-8), CM16 = splat2(-16), CM32 = splat2(-32), CM64 = splat2(-64);
@@ -116,6 +84,7 @@ void k_extd2_lanes(const DpJob *__restrict__ jobs, uint32_t n_jobs, PkBases base
 		if (jid >= n_jobs) break;
 		const DpJob J = jobs[jid];
 		const uint64_t t_base = J.t_off, q_base = J.q_off;          // base positions in the packed store
+		const SeqView SV(bases, J);
 		const int qlen = J.qlen, tlen = J.tlen, flag = J.flag, zdrop = J.zdrop, end_bonus = J.end_bonus;
 		const bool approx_max = flag & EZ_APPROX_MAX, right = flag & EZ_RIGHT;
 		int w = J.w;
@@ -123,13 +92,6 @@ void k_extd2_lanes(const DpJob *__restrict__ jobs, uint32_t n_jobs, PkBases base
 		const int T = (tlen + 15) / 16 * 16;
 		int n_col = qlen < tlen ? qlen : tlen;
 		n_col = (((n_col < w + 1 ? n_col : w + 1) + 15) / 16 + 1) * 16;
-		auto target_at = [&](int i) -> uint32_t { return (i >= 0 && i < tlen) ? (uint32_t)bases.at(t_base + (uint64_t)(J.seq_rev ? tlen - 1 - i : i)) : 0u; };
-		auto query_at = [&](int j) -> int {
-			int pj = J.qs + (J.seq_rev ? qlen - 1 - j : j);
-			if (!J.q_rev) return bases.at(q_base + (uint64_t)(pj));
-			int c = bases.at(q_base + (uint64_t)(J.qlen_full - 1 - pj));
-			return c < 4 ? 3 - c : 4;
-		};
 		// the windows, sixteen bases per thread and trip: consecutive j are consecutive store positions, ascending or descending (two word
 		// loads + two mask loads per sixteen bases instead of thirty-two loads); bytes 0..3 = ACGT, 4 = anything else
 		{
@@ -138,7 +100,7 @@ void k_extd2_lanes(const DpJob *__restrict__ jobs, uint32_t n_jobs, PkBases base
 			const uint32_t cm = J.q_rev ? 0x03030303u : 0u;
 			for (int j0 = 16 * tid; j0 < qlen; j0 += 16 * NT) {
 				const int64_t lo = q_desc ? q_p0 - j0 - 15 : q_p0 + j0;
-				if (lo < 0) { for (int j = j0; j < j0 + 16 && j < qlen; ++j) qq[j] = (uint8_t)query_at(j); continue; }
+				if (lo < 0) { for (int j = j0; j < j0 + 16 && j < qlen; ++j) qq[j] = (uint8_t)SV.query_in(j); continue; }
 				uint32_t w, m; bases.window16((uint64_t)lo, w, m);
 				if (q_desc) { w = __brev(w); w = ((w >> 1) & 0x55555555u) | ((w & 0x55555555u) << 1); m = __brev(m) >> 16; }
 				uint4 o; uint32_t *op = &o.x;
@@ -155,7 +117,7 @@ void k_extd2_lanes(const DpJob *__restrict__ jobs, uint32_t n_jobs, PkBases base
 				uint4 o = make_uint4(0u, 0u, 0u, 0u);
 				if (i0 < tlen) {
 					const int64_t lo = J.seq_rev ? t_p0 - i0 - 15 : t_p0 + i0;
-					if (lo < 0) { uint32_t *op = &o.x; for (int i = i0; i < i0 + 16; ++i) op[(i - i0) >> 2] |= target_at(i) << (8 * ((i - i0) & 3)); }
+					if (lo < 0) { uint32_t *op = &o.x; for (int i = i0; i < i0 + 16; ++i) op[(i - i0) >> 2] |= (uint32_t)SV.target_any(i) << (8 * ((i - i0) & 3)); }
 					else {
 						uint32_t w, m; bases.window16((uint64_t)lo, w, m);
 						if (J.seq_rev) { w = __brev(w); w = ((w >> 1) & 0x55555555u) | ((w & 0x55555555u) << 1); m = __brev(m) >> 16; }
@@ -260,7 +222,7 @@ void k_extd2_lanes(const DpJob *__restrict__ jobs, uint32_t n_jobs, PkBases base
 		for (int r = 0; r < n_diag; ++r) {
 			r_done = r + 1;
 			int st0, en0;
-			diag_range_l(r, qlen, tlen, w, st0, en0);
+			diag_range(r, qlen, tlen, w, st0, en0);
 			if (st0 > en0) { ez_zdropped = 1; break; }
 			const int st = st0 & ~15, en = ((en0 + 16) & ~15) - 1;         // (0 <= st0 <= en0: the reference's divisions by 16 are shifts)
 			const int span = ((en0 - st0) & ~15) + 16;
@@ -294,7 +256,7 @@ void k_extd2_lanes(const DpJob *__restrict__ jobs, uint32_t n_jobs, PkBases base
 			const int hp_in = wave_shr1(H[7], (int)nrec.z);
 			{
 				const uint32_t c1 = (uint32_t)(uint8_t)(-q - e), c2 = (uint32_t)(uint8_t)(-q2 - e2);
-				const uint32_t v1 = st > 0 ? c1 : (uint32_t)(uint8_t)(r == 0 ? -q - e : r < long_thres ? -e : r == long_thres ? long_diff : -e2);
+				const uint32_t v1 = st > 0 ? c1 : (uint32_t)(uint8_t)G.first_row(r);
 				const bool fresh_edge = st == 0 || !(st - 1 >= last_st && st - 1 <= last_en);     // (uniform)
 				inc = (t0 == st && fresh_edge) ? (c1 | v1 << 8 | c2 << 16) : inc;
 			}
@@ -316,7 +278,7 @@ void k_extd2_lanes(const DpJob *__restrict__ jobs, uint32_t n_jobs, PkBases base
 			if (t0 >= st && t0 <= en) {
 				// the column that joins on this diagonal starts from the first-row values
 				if (en >= r && r >= t0 && r < t0 + 8) {
-					const int uj = r == 0 ? -q - e : r < long_thres ? -e : r == long_thres ? long_diff : -e2;
+					const int uj = G.first_row(r);
 #pragma unroll
 					for (int p = 0; p < 4; ++p) {
 						if (t0 + 2 * p == r) { U[p].x = (short)(uj << 8); Y[p].x = (short)((-q - e) << 8); Y2[p].x = (short)((-q2 - e2) << 8); }
@@ -344,69 +306,69 @@ void k_extd2_lanes(const DpJob *__restrict__ jobs, uint32_t n_jobs, PkBases base
 					// the first of z, a, b, a2, b2 that attains the maximum = how many running maxima stay below it
 					s2_t p1[4], p2[4], p3[4];
 #pragma unroll
-					for (int p = 0; p < 4; ++p) p1[p] = k_max(z0[p], a[p]);
+					for (int p = 0; p < 4; ++p) p1[p] = pk_max(z0[p], a[p]);
 #pragma unroll
-					for (int p = 0; p < 4; ++p) p2[p] = k_max(p1[p], b[p]);
+					for (int p = 0; p < 4; ++p) p2[p] = pk_max(p1[p], b[p]);
 #pragma unroll
-					for (int p = 0; p < 4; ++p) p3[p] = k_max(p2[p], a2[p]);
+					for (int p = 0; p < 4; ++p) p3[p] = pk_max(p2[p], a2[p]);
 #pragma unroll
-					for (int p = 0; p < 4; ++p) zm[p] = k_max(p3[p], b2[p]);
+					for (int p = 0; p < 4; ++p) zm[p] = pk_max(p3[p], b2[p]);
 #pragma unroll
-					for (int p = 0; p < 4; ++p) d[p] = k_minu(zm[p] - z0[p], ONE);
+					for (int p = 0; p < 4; ++p) d[p] = pk_minu(zm[p] - z0[p], ONE);
 #pragma unroll
-					for (int p = 0; p < 4; ++p) d[p] = d[p] + k_minu(zm[p] - p1[p], ONE);
+					for (int p = 0; p < 4; ++p) d[p] = d[p] + pk_minu(zm[p] - p1[p], ONE);
 #pragma unroll
-					for (int p = 0; p < 4; ++p) d[p] = d[p] + k_minu(zm[p] - p2[p], ONE);
+					for (int p = 0; p < 4; ++p) d[p] = d[p] + pk_minu(zm[p] - p2[p], ONE);
 #pragma unroll
-					for (int p = 0; p < 4; ++p) d[p] = d[p] + k_minu(zm[p] - p3[p], ONE);
+					for (int p = 0; p < 4; ++p) d[p] = d[p] + pk_minu(zm[p] - p3[p], ONE);
 				} else {
 					// the last one that attains it = how many maxima over a suffix reach it
 					s2_t s3[4], s2[4], s1[4];
 #pragma unroll
-					for (int p = 0; p < 4; ++p) s3[p] = k_max(a2[p], b2[p]);
+					for (int p = 0; p < 4; ++p) s3[p] = pk_max(a2[p], b2[p]);
 #pragma unroll
-					for (int p = 0; p < 4; ++p) s2[p] = k_max(b[p], s3[p]);
+					for (int p = 0; p < 4; ++p) s2[p] = pk_max(b[p], s3[p]);
 #pragma unroll
-					for (int p = 0; p < 4; ++p) s1[p] = k_max(a[p], s2[p]);
+					for (int p = 0; p < 4; ++p) s1[p] = pk_max(a[p], s2[p]);
 #pragma unroll
-					for (int p = 0; p < 4; ++p) zm[p] = k_max(z0[p], s1[p]);
+					for (int p = 0; p < 4; ++p) zm[p] = pk_max(z0[p], s1[p]);
 #pragma unroll
-					for (int p = 0; p < 4; ++p) d[p] = FOUR - k_minu(zm[p] - b2[p], ONE);
+					for (int p = 0; p < 4; ++p) d[p] = FOUR - pk_minu(zm[p] - b2[p], ONE);
 #pragma unroll
-					for (int p = 0; p < 4; ++p) d[p] = d[p] - k_minu(zm[p] - s3[p], ONE);
+					for (int p = 0; p < 4; ++p) d[p] = d[p] - pk_minu(zm[p] - s3[p], ONE);
 #pragma unroll
-					for (int p = 0; p < 4; ++p) d[p] = d[p] - k_minu(zm[p] - s2[p], ONE);
+					for (int p = 0; p < 4; ++p) d[p] = d[p] - pk_minu(zm[p] - s2[p], ONE);
 #pragma unroll
-					for (int p = 0; p < 4; ++p) d[p] = d[p] - k_minu(zm[p] - s1[p], ONE);
+					for (int p = 0; p < 4; ++p) d[p] = d[p] - pk_minu(zm[p] - s1[p], ONE);
 				}
 #pragma unroll
-				for (int p = 0; p < 4; ++p) z[p] = k_min(zm[p], MCH);
+				for (int p = 0; p < 4; ++p) z[p] = pk_min(zm[p], MCH);
 #pragma unroll
 				for (int p = 0; p < 4; ++p) { const s2_t un = z[p] - vt1[p], vn = z[p] - U[p]; U[p] = un; V[p] = vn; }
 #pragma unroll
 				for (int p = 0; p < 4; ++p) { const s2_t t1 = z[p] - Q1, t2 = z[p] - Q2; a[p] = a[p] - t1; b[p] = b[p] - t1; a2[p] = a2[p] - t2; b2[p] = b2[p] - t2; }
 				if constexpr (!RIGHT) {                  // continuation bits: a > 0
 #pragma unroll
-					for (int p = 0; p < 4; ++p) { a[p] = k_max(a[p], ZERO); b[p] = k_max(b[p], ZERO); a2[p] = k_max(a2[p], ZERO); b2[p] = k_max(b2[p], ZERO); }
+					for (int p = 0; p < 4; ++p) { a[p] = pk_max(a[p], ZERO); b[p] = pk_max(b[p], ZERO); a2[p] = pk_max(a2[p], ZERO); b2[p] = pk_max(b2[p], ZERO); }
 #pragma unroll
-					for (int p = 0; p < 4; ++p) d[p] = k_mad(k_min(a[p], ONE), C8, d[p]);
+					for (int p = 0; p < 4; ++p) d[p] = pk_mad(pk_min(a[p], ONE), C8, d[p]);
 #pragma unroll
-					for (int p = 0; p < 4; ++p) d[p] = k_mad(k_min(b[p], ONE), C16, d[p]);
+					for (int p = 0; p < 4; ++p) d[p] = pk_mad(pk_min(b[p], ONE), C16, d[p]);
 #pragma unroll
-					for (int p = 0; p < 4; ++p) d[p] = k_mad(k_min(a2[p], ONE), C32, d[p]);
+					for (int p = 0; p < 4; ++p) d[p] = pk_mad(pk_min(a2[p], ONE), C32, d[p]);
 #pragma unroll
-					for (int p = 0; p < 4; ++p) d[p] = k_mad(k_min(b2[p], ONE), C64, d[p]);
+					for (int p = 0; p < 4; ++p) d[p] = pk_mad(pk_min(b2[p], ONE), C64, d[p]);
 				} else {                                 // a >= 0: all of 0x78 minus the sign bits
 #pragma unroll
-					for (int p = 0; p < 4; ++p) d[p] = k_mad(k_shr(C15, a[p]), CM8, d[p] + C120);
+					for (int p = 0; p < 4; ++p) d[p] = pk_mad(pk_shr(C15, a[p]), CM8, d[p] + C120);
 #pragma unroll
-					for (int p = 0; p < 4; ++p) d[p] = k_mad(k_shr(C15, b[p]), CM16, d[p]);
+					for (int p = 0; p < 4; ++p) d[p] = pk_mad(pk_shr(C15, b[p]), CM16, d[p]);
 #pragma unroll
-					for (int p = 0; p < 4; ++p) d[p] = k_mad(k_shr(C15, a2[p]), CM32, d[p]);
+					for (int p = 0; p < 4; ++p) d[p] = pk_mad(pk_shr(C15, a2[p]), CM32, d[p]);
 #pragma unroll
-					for (int p = 0; p < 4; ++p) d[p] = k_mad(k_shr(C15, b2[p]), CM64, d[p]);
+					for (int p = 0; p < 4; ++p) d[p] = pk_mad(pk_shr(C15, b2[p]), CM64, d[p]);
 #pragma unroll
-					for (int p = 0; p < 4; ++p) { a[p] = k_max(a[p], ZERO); b[p] = k_max(b[p], ZERO); a2[p] = k_max(a2[p], ZERO); b2[p] = k_max(b2[p], ZERO); }
+					for (int p = 0; p < 4; ++p) { a[p] = pk_max(a[p], ZERO); b[p] = pk_max(b[p], ZERO); a2[p] = pk_max(a2[p], ZERO); b2[p] = pk_max(b2[p], ZERO); }
 				}
 #pragma unroll
 				for (int p = 0; p < 4; ++p) { X[p] = a[p] - QE; Y[p] = b[p] - QE; X2[p] = a2[p] - QE2; Y2[p] = b2[p] - QE2; dpk[p] = (uint32_t)as_i(d[p]); }
@@ -556,7 +518,7 @@ void k_extd2_lanes(const DpJob *__restrict__ jobs, uint32_t n_jobs, PkBases base
 		                                  pf[8] / r_done, pf[5] / r_done, pf[6] / r_done, pf[7] / r_done, pf[0] / r_done, pf[1] / r_done, pf[2] / r_done, pf[3] / r_done, pf[4] / r_done);
 #endif
 		// ---- backtrack by wave 0 (ksw2.h:127-159) through a 64x64 LDS window of the direction matrix ----
-		int n_cigar = 0, bi = -1, bj = -1;
+		int bi = -1, bj = -1;
 		const bool lb_broken = lb_hit && !sat && !(ez_zdropped && ez_max == lb_max && ez_max_t == lb_max_t && ez_max_q == lb_max_q && ez_mte == lb_mte && ez_mte_q == lb_mte_q &&
 		                                            ez_mqe == KSW_NEG_INF && ez_score == KSW_NEG_INF);
 		if (sat) {}                                                 // (no traceback: the problem is redone)
@@ -566,73 +528,17 @@ void k_extd2_lanes(const DpJob *__restrict__ jobs, uint32_t n_jobs, PkBases base
 		__threadfence_block();
 		__syncthreads();
 		if (wave == 0) {
-			int i = bi, j = bj, state = 0; long long guard = 0;
-			uint32_t last_op = 0xffffffffu, run_len = 0;
-			auto cg_push = [&](uint32_t op, uint32_t len) {
-				if (op == last_op) { run_len += len; return; }
-				if (last_op != 0xffffffffu) { if (lane == 0) cig_tmp[n_cigar] = run_len << 4 | last_op; ++n_cigar; }
-				last_op = op; run_len = len;
-			};
-			auto cg_flush = [&] { if (last_op != 0xffffffffu && n_cigar >= 0) { if (lane == 0) cig_tmp[n_cigar] = run_len << 4 | last_op; ++n_cigar; last_op = 0xffffffffu; } };
-			while (i >= 0 && j >= 0) {
-				if (++guard > 4000000) { n_cigar = -7; break; }
-				const int r_hi = i + j, c_lo = i - (LBT - 1);
-				{
-					uint8_t wv[LBT];
-#pragma unroll
-					for (int row = 0; row < LBT; ++row) {
-						const int r = r_hi - row, col = c_lo + lane;
-						uint8_t val = 0;
-						if (r >= 0 && col >= 0) {
-							int st0, en0; diag_range_l(r, qlen, tlen, w, st0, en0);
-							const int off = st0 / 16 * 16, off_end = (en0 + 16) / 16 * 16 - 1;
-							if (st0 <= en0 && col >= off && col <= off_end) val = pool_base[(size_t)s_chunk[r / rpc] * CHUNK + (size_t)(r % rpc) * n_col + (col - off)];
-						}
-						wv[row] = val;
-					}
-#pragma unroll
-					for (int row = 0; row < LBT; ++row) s_win[row * LBT + lane] = wv[row];
-				}
-				__builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
-				while (i >= 0 && j >= 0) {
-					const int r = i + j, row = r_hi - r;
-					if (row >= LBT || i < c_lo) break;
-					int st0, en0; diag_range_l(r, qlen, tlen, w, st0, en0);
+			long long guard = 0;
+			const int n_cigar = backtrack_windowed<BT_WIN, false>(lane, bi, bj, s_win, cig_tmp, guard, 4000000,
+				[&](int r, int &st0, int &en0) { diag_range(r, qlen, tlen, w, st0, en0); },
+				[&](int r, int col) -> uint8_t {                       // stored: the sixteen-rounded range; the matrix lies in the workgroup's chunks
+					int st0, en0; diag_range(r, qlen, tlen, w, st0, en0);
 					const int off = st0 / 16 * 16, off_end = (en0 + 16) / 16 * 16 - 1;
-					int force_state = -1;
-					if (i < off) force_state = 2;
-					if (i > off_end) force_state = 1;
-					const uint32_t tmp = force_state < 0 ? s_win[row * LBT + (i - c_lo)] : 0;
-					if (state == 0) state = tmp & 7;
-					else if (!(tmp >> (state + 2) & 1)) state = 0;
-					if (state == 0) state = tmp & 7;
-					if (force_state >= 0) state = force_state;
-					uint32_t op;
-					if (state == 0) op = 0, --i, --j;
-					else if (state == 1 || state == 3) op = 2, --i;
-					else op = 1, --j;
-					cg_push(op, 1u);
-				}
-				__builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
-			}
-			if (bi >= 0 && bj >= 0 && n_cigar >= 0) {
-				if (i >= 0) cg_push(2u, (uint32_t)(i + 1));
-				if (j >= 0) cg_push(1u, (uint32_t)(j + 1));
-			}
-			cg_flush();
-			unsigned long long base = 0;
-			if (lane == 0 && n_cigar > 0) base = atomicAdd(pool_cursor, (unsigned long long)n_cigar);
-			base = ((unsigned long long)(unsigned)__shfl((int)(base >> 32), 0) << 32) | (unsigned)__shfl((int)(base & 0xffffffffULL), 0);
-			__builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
-			const bool rev_cigar = flag & EZ_REV_CIGAR;
-			if (n_cigar > 0 && base + (unsigned long long)n_cigar <= pool_cap)
-				for (int c = lane; c < n_cigar; c += 64) cigar_pool[base + c] = rev_cigar ? cig_tmp[c] : cig_tmp[n_cigar - 1 - c];
-			if (lane == 0) {
-				DpRes R;
-				R.max = ez_max, R.max_q = ez_max_q, R.max_t = ez_max_t, R.mqe = ez_mqe, R.mqe_t = ez_mqe_t, R.mte = ez_mte, R.mte_q = ez_mte_q;
-				R.score = ez_score, R.zdropped = ez_zdropped, R.reach_end = ez_reach_end, R.n_cigar = lb_broken ? -11 : sat ? -9 : n_cigar, R.pad = r_done, R.cigar_off = base;
-				res[jid] = R;
-			}
+					return st0 <= en0 && col >= off && col <= off_end ? pool_base[(size_t)s_chunk[r / rpc] * CHUNK + (size_t)(r % rpc) * n_col + (col - off)] : (uint8_t)0;
+				});
+			DpRes R = ez_record(ez_max, ez_max_q, ez_max_t, ez_mqe, ez_mqe_t, ez_mte, ez_mte_q, ez_score, ez_zdropped, ez_reach_end);
+			R.n_cigar = lb_broken ? -11 : sat ? -9 : n_cigar, R.pad = r_done;
+			cigar_commit<true, true>(lane, n_cigar, flag & EZ_REV_CIGAR, cig_tmp, cigar_pool, pool_cursor, pool_cap, R, &res[jid]);
 		}
 	}
 }
@@ -661,12 +567,7 @@ size_t lanes_chunk_bytes(int nt) { return lanes_chunk_of(nt); }
 template <int NT> static void launch_lanes_nt(unsigned n_blocks, size_t lds, hipStream_t st, const DpJob *jobs, uint32_t n_jobs, PkBases bases, const DpParams &P, uint32_t *counter, uint8_t *slab,
                                               size_t cig_bytes, uint32_t n_chunks, int q_cap, DpRes *res, uint32_t *pool, unsigned long long *cursor, unsigned long long pool_cap)
 {
-	{	// a per-DEVICE function attribute, set once per device whatever thread comes first
-		static std::mutex mu; static bool attr_set[64] = {};
-		int dev = 0; PGA_HIP(hipGetDevice(&dev));
-		std::lock_guard<std::mutex> lk(mu);
-		if (!attr_set[dev & 63]) { PGA_HIP(hipFuncSetAttribute((const void*)k_extd2_lanes<NT>, hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024)); attr_set[dev & 63] = true; }
-	}
+	set_max_dynamic_lds_once((const void*)k_extd2_lanes<NT>, 64 * 1024);
 	hipLaunchKernelGGL(k_extd2_lanes<NT>, dim3(n_blocks), dim3(NT), lds, st, jobs, n_jobs, bases, P, counter, slab, cig_bytes, n_chunks, q_cap, res, pool, cursor, pool_cap);
 }
 

@@ -22,10 +22,8 @@
 //     blocks the band needs at once.
 // A clamped maximum hands the problem back to the workgroup kernel (n_cigar = -9), a dry chunk pool to the lane kernel (-10).  Semantics (16-lane rounding of the ranges, stale rows outside them, the
 // first-row and fresh-edge rules, int8 wrap-around) are the lane kernel's; parity: tests/test_gpu_parity.py (PGA_PIPE=force / off).
-#include <mutex>
 #include "pga_common.h"
-#include "pga_dp.h"
-#include "pga_wave.h"
+#include "pga_ksw_shared.h"
 #include "pga_pk16.h"
 #include <cstdio>
 #include <cstring>
@@ -33,11 +31,6 @@
 
 namespace pga {
 
-#define KSW_NEG_INF (-0x40000000)
-#define EZ_RIGHT      0x02
-#define EZ_APPROX_MAX 0x08
-#define EZ_EXTZ_ONLY  0x40
-#define EZ_REV_CIGAR  0x80
 #define PP_NW 8
 #define PP_C 4
 #define PP_WCOLS (64 * PP_C)
@@ -47,17 +40,7 @@ namespace pga {
 #define PP_NT ((PP_NW + 1) * 64)
 #define PP_CHUNK (2u << 20)
 #define PP_MAXCHUNK 192
-#define PP_BT 64
 
-__device__ __forceinline__ void pp_range(int r, int qlen, int tlen, int w, int &st0, int &en0)
-{
-	int st = 0, en = tlen - 1;
-	if (st < r - qlen + 1) st = r - qlen + 1;
-	if (en > r) en = r;
-	if (st < (r - w + 1) >> 1) st = (r - w + 1) >> 1;
-	if (en > (r + w) >> 1) en = (r + w) >> 1;
-	st0 = st, en0 = en;
-}
 // the last column a diagonal touches: the sixteen-rounded range or the score bytes it refreshes, whichever reaches further (capped at the padded target)
 __device__ __forceinline__ int pp_hi(int st0, int en0, int T)
 {
@@ -65,11 +48,6 @@ __device__ __forceinline__ int pp_hi(int st0, int en0, int T)
 	int h = en > sp ? en : sp;
 	return h > T - 1 ? T - 1 : h;
 }
-__device__ __forceinline__ s2_t pk_max(s2_t a, s2_t b) { int r; asm("v_pk_max_i16 %0, %1, %2" : "=v"(r) : "v"(as_i(a)), "v"(as_i(b))); return as_s2(r); }
-__device__ __forceinline__ s2_t pk_min(s2_t a, s2_t b) { int r; asm("v_pk_min_i16 %0, %1, %2" : "=v"(r) : "v"(as_i(a)), "v"(as_i(b))); return as_s2(r); }
-__device__ __forceinline__ s2_t pk_minu(s2_t a, s2_t b) { int r; asm("v_pk_min_u16 %0, %1, %2" : "=v"(r) : "v"(as_i(a)), "v"(as_i(b))); return as_s2(r); }
-__device__ __forceinline__ s2_t pk_mad(s2_t a, s2_t b, s2_t c) { int r; asm("v_pk_mad_u16 %0, %1, %2, %3" : "=v"(r) : "v"(as_i(a)), "v"(as_i(b)), "v"(as_i(c))); return as_s2(r); }
-__device__ __forceinline__ s2_t pk_shr(s2_t sh, s2_t a) { int r; asm("v_pk_lshrrev_b16 %0, %1, %2" : "=v"(r) : "v"(as_i(sh)), "v"(as_i(a))); return as_s2(r); }
 
 __device__ __forceinline__ int pp_ld(const int *p) { return __hip_atomic_load(p, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP); }
 __device__ __forceinline__ void pp_st(int *p, int v) { __hip_atomic_store(p, v, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP); }
@@ -88,19 +66,14 @@ void k_ext_pipe(const DpJob *__restrict__ jobs, uint32_t n_jobs, PkBases bases, 
 	__shared__ int s_eval, s_stop, s_nlim, s_kind, s_dry;
 	__shared__ uint32_t s_chunk[PP_MAXCHUNK];
 	__shared__ int s_have;
-	__shared__ uint8_t s_win[PP_BT * PP_BT];
+	__shared__ uint8_t s_win[BT_WIN * BT_WIN];
 	const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
 	uint32_t *cig_tmp = (uint32_t*)(slab_all + (size_t)blockIdx.x * cig_bytes);
 	uint8_t *pool_base = slab_all + (size_t)gridDim.x * cig_bytes;
 	if (tid == 0) s_have = 0;
-	int q = P.q, e = P.e, q2 = P.q2, e2 = P.e2;
-	const int qe_h = q + e;
-	if (q2 + e2 < q + e) { int t = q; q = q2, q2 = t, t = e, e = e2, e2 = t; }
-	const int qe = q + e, qe2 = q2 + e2;
-	const int sc_mch = P.sc_mch, sc_mis = P.sc_mis, sc_N = P.sc_ambi == 0 ? -e2 : P.sc_ambi;
-	int long_thres = e != e2 ? (q2 - q) / (e - e2) - 1 : 0;
-	if (q2 + e2 + long_thres * e2 > q + e + long_thres * e) ++long_thres;
-	const int long_diff = long_thres * (e - e2) - (q2 - q) - e2;
+	const GapCosts G(P);
+	const int q = G.q, e = G.e, q2 = G.q2, e2 = G.e2, qe_h = G.qe_h, qe = G.qe, qe2 = G.qe2;
+	const int sc_mch = P.sc_mch, sc_mis = P.sc_mis, sc_N = G.sc_N;
 	const uint32_t sc_tab = (uint32_t)(uint8_t)sc_mch | (uint32_t)(uint8_t)sc_mis << 8 | (uint32_t)(uint8_t)sc_N << 16 | (uint32_t)(uint8_t)sc_N << 24;
 	const s2_t ZERO = splat2(0), ONE = splat2(1), FOUR = splat2(4), MCH = splat2(sc_mch << 8), Q1 = splat2(q << 8), Q2 = splat2(q2 << 8), QE = splat2(qe << 8), QE2 = splat2(qe2 << 8);
 	const s2_t C8 = splat2(8), C16 = splat2(16), C32 = splat2(32), C64 = splat2(64), C120 = splat2(120), C15 = splat2(15), CM8 = splat2(-8), CM16 = splat2(-16), CM32 = splat2(-32), CM64 = splat2(-64);
@@ -116,6 +89,7 @@ void k_ext_pipe(const DpJob *__restrict__ jobs, uint32_t n_jobs, PkBases bases, 
 		if (jid >= n_jobs) break;
 		const DpJob J = jobs[jid];
 		const uint64_t t_base = J.t_off, q_base = J.q_off;
+		const SeqView SV(bases, J);
 		const int qlen = J.qlen, tlen = J.tlen, flag = J.flag, zdrop = J.zdrop, end_bonus = J.end_bonus;
 		const bool right = flag & EZ_RIGHT;
 		int w = J.w;
@@ -125,13 +99,6 @@ void k_ext_pipe(const DpJob *__restrict__ jobs, uint32_t n_jobs, PkBases bases, 
 		n_col = (((n_col < w + 1 ? n_col : w + 1) + 15) / 16 + 1) * 16;
 		const int n_diag = qlen + tlen - 1;
 		const int rpc = PP_CHUNK / n_col;
-		auto target_at = [&](int i) -> uint32_t { return (i >= 0 && i < tlen) ? (uint32_t)bases.at(t_base + (uint64_t)(J.seq_rev ? tlen - 1 - i : i)) : 0u; };
-		auto query_at = [&](int j) -> int {
-			int pj = J.qs + (J.seq_rev ? qlen - 1 - j : j);
-			if (!J.q_rev) return bases.at(q_base + (uint64_t)(pj));
-			int c = bases.at(q_base + (uint64_t)(J.qlen_full - 1 - pj));
-			return c < 4 ? 3 - c : 4;
-		};
 		// the windows, sixteen bases per thread and trip (the lane kernel's staging): bytes 0..3 = ACGT, 4 = anything else
 		{
 			const bool q_desc = (J.seq_rev != 0) != (J.q_rev != 0);
@@ -139,7 +106,7 @@ void k_ext_pipe(const DpJob *__restrict__ jobs, uint32_t n_jobs, PkBases bases, 
 			const uint32_t cm = J.q_rev ? 0x03030303u : 0u;
 			for (int j0 = 16 * tid; j0 < qlen; j0 += 16 * PP_NT) {
 				const int64_t lo = q_desc ? q_p0 - j0 - 15 : q_p0 + j0;
-				if (lo < 0) { for (int j = j0; j < j0 + 16 && j < qlen; ++j) qq[j] = (uint8_t)query_at(j); continue; }
+				if (lo < 0) { for (int j = j0; j < j0 + 16 && j < qlen; ++j) qq[j] = (uint8_t)SV.query_in(j); continue; }
 				uint32_t ww, m; bases.window16((uint64_t)lo, ww, m);
 				if (q_desc) { ww = __brev(ww); ww = ((ww >> 1) & 0x55555555u) | ((ww & 0x55555555u) << 1); m = __brev(m) >> 16; }
 				uint4 o; uint32_t *op = &o.x;
@@ -156,7 +123,7 @@ void k_ext_pipe(const DpJob *__restrict__ jobs, uint32_t n_jobs, PkBases bases, 
 				uint4 o = make_uint4(0u, 0u, 0u, 0u);
 				if (i0 < tlen) {
 					const int64_t lo = J.seq_rev ? t_p0 - i0 - 15 : t_p0 + i0;
-					if (lo < 0) { uint32_t *op = &o.x; for (int i = i0; i < i0 + 16; ++i) op[(i - i0) >> 2] |= target_at(i) << (8 * ((i - i0) & 3)); }
+					if (lo < 0) { uint32_t *op = &o.x; for (int i = i0; i < i0 + 16; ++i) op[(i - i0) >> 2] |= (uint32_t)SV.target_any(i) << (8 * ((i - i0) & 3)); }
 					else {
 						uint32_t ww, m; bases.window16((uint64_t)lo, ww, m);
 						if (J.seq_rev) { ww = __brev(ww); ww = ((ww >> 1) & 0x55555555u) | ((ww & 0x55555555u) << 1); m = __brev(m) >> 16; }
@@ -179,7 +146,7 @@ void k_ext_pipe(const DpJob *__restrict__ jobs, uint32_t n_jobs, PkBases bases, 
 			// the first diagonal whose range is empty (the reference ends there, zdropped; monotone in r), else the end of the matrix
 			int lo = 0, hi = n_diag;
 			while (lo < hi) {
-				const int mid = (lo + hi) >> 1; int a0, a1; pp_range(mid, qlen, tlen, w, a0, a1);
+				const int mid = (lo + hi) >> 1; int a0, a1; diag_range(mid, qlen, tlen, w, a0, a1);
 				if (a0 > a1) hi = mid; else lo = mid + 1;
 			}
 			s_nlim = lo; s_kind = lo < n_diag ? 1 : 0;
@@ -232,14 +199,14 @@ void k_ext_pipe(const DpJob *__restrict__ jobs, uint32_t n_jobs, PkBases bases, 
 				if (pp_ld(&s_stop)) break;
 				// has the band reached this wave?  has it left it?  (ranges only move to the right)
 				int a0, a1, b0, b1;
-				pp_range(r0, qlen, tlen, w, b0, b1);
+				diag_range(r0, qlen, tlen, w, b0, b1);
 				bool gone = false;
 				while ((b0 & ~15) > col_lo + PP_WCOLS - 1) {                          // the band has left the block: the next turn of the ring, if the target goes that far
 					if (col_lo + PP_RING > T - 1) { gone = true; break; }
 					col_lo += PP_RING; take_block();
 				}
 				if (gone) break;                                                     // (progress is raised behind the loop)
-				pp_range(r1, qlen, tlen, w, a0, a1);
+				diag_range(r1, qlen, tlen, w, a0, a1);
 				if (pp_hi(a0, a1, T) < col_lo) { if (lane == 0) pp_st(&s_prog[k], r1 + 1); continue; }
 				// the wave on the left has finished these diagonals; the evaluator (and with it the wave on the right) has read the ring slots they reuse;
 				// the rows' chunk exists
@@ -255,7 +222,7 @@ void k_ext_pipe(const DpJob *__restrict__ jobs, uint32_t n_jobs, PkBases bases, 
 #pragma unroll
 					for (int i = 0; i < 4; ++i) { const int j = r0 - 1 - i - t0; W |= ((j >= 0 && j < qlen) ? (uint32_t)qq[j] : 0u) << (8 * i); }
 					{ const int j = r0 - t0; q_next = (j >= 0 && j < qlen) ? (uint32_t)qq[j] : 0u; }
-					if (r0 > 0) { int c0, c1; pp_range(r0 - 1, qlen, tlen, w, c0, c1); last_st = c0 & ~15, last_en = ((c1 + 16) & ~15) - 1; }
+					if (r0 > 0) { int c0, c1; diag_range(r0 - 1, qlen, tlen, w, c0, c1); last_st = c0 & ~15, last_en = ((c1 + 16) & ~15) - 1; }
 				}
 				// the left wave's last column after the diagonals r0 - 1 ... r1 - 1, a diagonal per lane
 				unsigned long long inw = (unsigned long long)(uint32_t)KSW_NEG_INF << 32 | nb_init;
@@ -265,7 +232,7 @@ void k_ext_pipe(const DpJob *__restrict__ jobs, uint32_t n_jobs, PkBases bases, 
 				for (int r = r0; r <= r1; ++r) {
 					const int di = r - r0;
 					int st0, en0;
-					pp_range(r, qlen, tlen, w, st0, en0);
+					diag_range(r, qlen, tlen, w, st0, en0);
 					const int st = st0 & ~15, en = ((en0 + 16) & ~15) - 1;
 					const int span = ((en0 - st0) & ~15) + 16;
 					W = W << 8 | q_next;
@@ -276,7 +243,7 @@ void k_ext_pipe(const DpJob *__restrict__ jobs, uint32_t n_jobs, PkBases bases, 
 					const int hp_in = wave_shr1(H[3], __builtin_amdgcn_readlane((int)(uint32_t)(inw >> 32), di));
 					{
 						const uint32_t c1 = (uint32_t)(uint8_t)(-q - e), c2 = (uint32_t)(uint8_t)(-q2 - e2);
-						const uint32_t v1 = st > 0 ? c1 : (uint32_t)(uint8_t)(r == 0 ? -q - e : r < long_thres ? -e : r == long_thres ? long_diff : -e2);
+						const uint32_t v1 = st > 0 ? c1 : (uint32_t)(uint8_t)G.first_row(r);
 						const bool fresh_edge = st == 0 || !(st - 1 >= last_st && st - 1 <= last_en);
 						inc = (t0 == st && fresh_edge) ? (c1 | v1 << 8 | c2 << 16) : inc;
 					}
@@ -290,7 +257,7 @@ void k_ext_pipe(const DpJob *__restrict__ jobs, uint32_t n_jobs, PkBases bases, 
 					}
 					if (t0 >= st && t0 <= en) {
 						if (en >= r && r >= t0 && r < t0 + 4) {
-							const int uj = r == 0 ? -q - e : r < long_thres ? -e : r == long_thres ? long_diff : -e2;
+							const int uj = G.first_row(r);
 #pragma unroll
 							for (int p = 0; p < 2; ++p) {
 								if (t0 + 2 * p == r) { U[p].x = (short)(uj << 8); Y[p].x = (short)((-q - e) << 8); Y2[p].x = (short)((-q2 - e2) << 8); }
@@ -479,7 +446,7 @@ void k_ext_pipe(const DpJob *__restrict__ jobs, uint32_t n_jobs, PkBases bases, 
 				// the keys of the block: lane = 16 * g + i holds diagonal r0 + i of the waves g and g + 4; a wave counts where the range touches its columns
 				const int i = lane & 15, g = lane >> 4, r = r0 + i;
 				int st0 = 0, en0 = -1;
-				if (r <= r1) pp_range(r, qlen, tlen, w, st0, en0);
+				if (r <= r1) diag_range(r, qlen, tlen, w, st0, en0);
 				uint32_t kk = 0;
 				if (r <= r1) {
 #pragma unroll
@@ -525,78 +492,23 @@ void k_ext_pipe(const DpJob *__restrict__ jobs, uint32_t n_jobs, PkBases bases, 
 		__syncthreads();
 		// ---- the evaluator walks the path back (ksw2.h:127-159) through a 64 x 64 LDS window of the direction matrix ----
 		if (wave == PP_NW) {
-			int n_cigar = 0, bi = -1, bj = -1;
+			int bi = -1, bj = -1;
 			if (sat) {}
 			else if (!ez_zdropped && !(flag & EZ_EXTZ_ONLY)) bi = tlen - 1, bj = qlen - 1;
 			else if (!ez_zdropped && (flag & EZ_EXTZ_ONLY) && ez_mqe + end_bonus > ez_max) ez_reach_end = 1, bi = ez_mqe_t, bj = qlen - 1;
 			else if (ez_max_t >= 0 && ez_max_q >= 0) bi = ez_max_t, bj = ez_max_q;
-			int i = bi, j = bj, state = 0; long long guard = 0;
-			uint32_t last_op = 0xffffffffu, run_len = 0;
-			auto cg_push = [&](uint32_t op, uint32_t len) {
-				if (op == last_op) { run_len += len; return; }
-				if (last_op != 0xffffffffu) { if (lane == 0) cig_tmp[n_cigar] = run_len << 4 | last_op; ++n_cigar; }
-				last_op = op; run_len = len;
-			};
-			auto cg_flush = [&] { if (last_op != 0xffffffffu && n_cigar >= 0) { if (lane == 0) cig_tmp[n_cigar] = run_len << 4 | last_op; ++n_cigar; last_op = 0xffffffffu; } };
-			while (i >= 0 && j >= 0) {
-				if (++guard > 4000000) { n_cigar = -7; break; }
-				const int r_hi = i + j, c_lo = i - (PP_BT - 1);
-				for (int part = 0; part < PP_BT; part += 8) {            // (eight loads in flight: the walk is a rare, short path and must not set the kernel's register count)
-					uint8_t wv[8];
-#pragma unroll
-					for (int rw = 0; rw < 8; ++rw) {
-						const int r = r_hi - (part + rw), col = c_lo + lane;
-						uint8_t val = 0;
-						if (r >= 0 && col >= 0) {
-							int st0, en0; pp_range(r, qlen, tlen, w, st0, en0);
-							const int off = st0 / 16 * 16, off_end = (en0 + 16) / 16 * 16 - 1;
-							if (st0 <= en0 && col >= off && col <= off_end) val = pool_base[(size_t)s_chunk[r / rpc] * PP_CHUNK + (size_t)(r % rpc) * n_col + (col - off)];
-						}
-						wv[rw] = val;
-					}
-#pragma unroll
-					for (int rw = 0; rw < 8; ++rw) s_win[(part + rw) * PP_BT + lane] = wv[rw];
-				}
-				__builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
-				while (i >= 0 && j >= 0) {
-					const int r = i + j, row = r_hi - r;
-					if (row >= PP_BT || i < c_lo) break;
-					int st0, en0; pp_range(r, qlen, tlen, w, st0, en0);
+			long long guard = 0;
+			// (eight loads in flight: the walk is a rare, short path and must not set the kernel's register count)
+			const int n_cigar = backtrack_windowed<8, false>(lane, bi, bj, s_win, cig_tmp, guard, 4000000,
+				[&](int r, int &st0, int &en0) { diag_range(r, qlen, tlen, w, st0, en0); },
+				[&](int r, int col) -> uint8_t {                       // stored: the sixteen-rounded range; the matrix lies in the workgroup's chunks
+					int st0, en0; diag_range(r, qlen, tlen, w, st0, en0);
 					const int off = st0 / 16 * 16, off_end = (en0 + 16) / 16 * 16 - 1;
-					int force_state = -1;
-					if (i < off) force_state = 2;
-					if (i > off_end) force_state = 1;
-					const uint32_t tmp = force_state < 0 ? s_win[row * PP_BT + (i - c_lo)] : 0;
-					if (state == 0) state = tmp & 7;
-					else if (!(tmp >> (state + 2) & 1)) state = 0;
-					if (state == 0) state = tmp & 7;
-					if (force_state >= 0) state = force_state;
-					uint32_t op;
-					if (state == 0) op = 0, --i, --j;
-					else if (state == 1 || state == 3) op = 2, --i;
-					else op = 1, --j;
-					cg_push(op, 1u);
-				}
-				__builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
-			}
-			if (bi >= 0 && bj >= 0 && n_cigar >= 0) {
-				if (i >= 0) cg_push(2u, (uint32_t)(i + 1));
-				if (j >= 0) cg_push(1u, (uint32_t)(j + 1));
-			}
-			cg_flush();
-			unsigned long long base = 0;
-			if (lane == 0 && n_cigar > 0) base = atomicAdd(pool_cursor, (unsigned long long)n_cigar);
-			base = ((unsigned long long)(unsigned)__shfl((int)(base >> 32), 0) << 32) | (unsigned)__shfl((int)(base & 0xffffffffULL), 0);
-			__builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
-			const bool rev_cigar = flag & EZ_REV_CIGAR;
-			if (n_cigar > 0 && base + (unsigned long long)n_cigar <= pool_cap)
-				for (int c = lane; c < n_cigar; c += 64) cigar_pool[base + c] = rev_cigar ? cig_tmp[c] : cig_tmp[n_cigar - 1 - c];
-			if (lane == 0) {
-				DpRes R;
-				R.max = ez_max, R.max_q = ez_max_q, R.max_t = ez_max_t, R.mqe = ez_mqe, R.mqe_t = ez_mqe_t, R.mte = ez_mte, R.mte_q = ez_mte_q;
-				R.score = ez_score, R.zdropped = ez_zdropped, R.reach_end = ez_reach_end, R.n_cigar = (sat & 1) ? -9 : sat ? -10 : n_cigar, R.pad = r_done, R.cigar_off = base;
-				res[jid] = R;
-			}
+					return st0 <= en0 && col >= off && col <= off_end ? pool_base[(size_t)s_chunk[r / rpc] * PP_CHUNK + (size_t)(r % rpc) * n_col + (col - off)] : (uint8_t)0;
+				});
+			DpRes R = ez_record(ez_max, ez_max_q, ez_max_t, ez_mqe, ez_mqe_t, ez_mte, ez_mte_q, ez_score, ez_zdropped, ez_reach_end);
+			R.n_cigar = (sat & 1) ? -9 : sat ? -10 : n_cigar, R.pad = r_done;
+			cigar_commit<true, true>(lane, n_cigar, flag & EZ_REV_CIGAR, cig_tmp, cigar_pool, pool_cursor, pool_cap, R, &res[jid]);
 		}
 	}
 }
@@ -628,12 +540,7 @@ void launch_ext_pipe(unsigned n_blocks, int q_cap, int t_cap, const DpJob *jobs,
                      DpRes *res, uint32_t *pool, unsigned long long *cursor, unsigned long long pool_cap, hipStream_t st)
 {
 	const size_t lds = (((size_t)q_cap + 15) & ~(size_t)15) + (((size_t)t_cap + 15) & ~(size_t)15) + 16;
-	{
-		static std::mutex mu; static bool attr_set[64] = {};
-		int dev = 0; PGA_HIP(hipGetDevice(&dev));
-		std::lock_guard<std::mutex> lk(mu);
-		if (!attr_set[dev & 63]) { PGA_HIP(hipFuncSetAttribute((const void*)k_ext_pipe, hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024)); attr_set[dev & 63] = true; }
-	}
+	set_max_dynamic_lds_once((const void*)k_ext_pipe, 64 * 1024);
 	hipLaunchKernelGGL(k_ext_pipe, dim3(n_blocks), dim3(PP_NT), lds, st, jobs, n_jobs, bases, P, counter, slab, pipe_cig_bytes(q_cap, t_cap), n_chunks, q_cap, res, pool, cursor, pool_cap);
 }
 

@@ -16,25 +16,16 @@
 // affine gap states of the recurrence charge an l-base gap (ksw2_extd2_sse.c: E = max(H - q, E) - e for both pairs, H = max of all).
 // Arithmetic and direction bytes are the packed two-column cell pass of pga_ksw_wide.hip (no int8 wrap inside an unbinding band).
 #include "pga_common.h"
-#include "pga_dp.h"
-#include "pga_wave.h"
+#include "pga_ksw_shared.h"
 #include "pga_pk16.h"
 #include <cstring>
 
 namespace pga {
 
-#define KSW_NEG_INF (-0x40000000)
 #define ST_S 512            // columns per strip (one pair of columns per compute thread and diagonal)
 #define ST_NT 256           // compute threads per workgroup: one pair of columns each per diagonal (256-column strips measured the same: the cost of a diagonal is its barrier and LDS round trips)
 #define ST_NTL 320          // launched threads: a fifth wave does nothing but fetch the left neighbour's boundary words
 #define ST_QMAX 12288       // longest query window
-#define ST_BT 64
-
-__device__ __forceinline__ void st_range(int r, int qlen, int tlen, int &st0, int &en0)
-{
-	st0 = r - qlen + 1 > 0 ? r - qlen + 1 : 0;
-	en0 = r < tlen - 1 ? r : tlen - 1;
-}
 
 __global__ __launch_bounds__(ST_NTL)
 void k_approx_strips(const DpJob *__restrict__ jobs, const uint32_t *__restrict__ blk_job, const uint32_t *__restrict__ blk_strip, PkBases bases, DpParams P,
@@ -45,7 +36,7 @@ void k_approx_strips(const DpJob *__restrict__ jobs, const uint32_t *__restrict_
 	__shared__ int8_t s_x[2][ST_S + 16], s_v[2][ST_S + 16], s_x2[2][ST_S + 16];
 	__shared__ uint8_t s_t[ST_S + 16];
 	__shared__ uint8_t s_q[ST_QMAX + 64];                 // query REVERSED with 32 zero bytes on either side: column t of diagonal r reads s_q[t + 32 + qlen-1-r]
-	__shared__ uint8_t s_win[ST_BT * ST_BT];
+	__shared__ uint8_t s_win[BT_WIN * BT_WIN];
 	__shared__ uint32_t s_last;
 	__shared__ uint32_t s_bnd[16];                        // boundary words of 2 x 8 diagonals: slot (d - first) & 15 holds bnd_in[d]
 	// exact-maximum problems (second passes: flag == 0): H of the strip's columns; H of the diagonal's LAST column (it runs along the first
@@ -58,18 +49,14 @@ void k_approx_strips(const DpJob *__restrict__ jobs, const uint32_t *__restrict_
 	const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
 	const uint32_t jl = blk_job[blockIdx.x], k = blk_strip[blockIdx.x];
 	const DpJob J = jobs[jl];
-	const uint64_t t_base = J.t_off, q_base = J.q_off;          // base positions in the packed store
+	const SeqView SV(bases, J);
 	const int qlen = J.qlen, tlen = J.tlen;
-	int q = P.q, e = P.e, q2 = P.q2, e2 = P.e2;
-	if (q2 + e2 < q + e) { int t = q; q = q2, q2 = t, t = e, e = e2, e2 = t; }
-	const int qe = q + e, qe2 = q2 + e2;
-	const int sc_mch = P.sc_mch, sc_mis = P.sc_mis, sc_N = P.sc_ambi == 0 ? -e2 : P.sc_ambi;
-	int long_thres = e != e2 ? (q2 - q) / (e - e2) - 1 : 0;
-	if (q2 + e2 + long_thres * e2 > q + e + long_thres * e) ++long_thres;
-	const int long_diff = long_thres * (e - e2) - (q2 - q) - e2;
+	const GapCosts G(P);
+	const int q = G.q, e = G.e, q2 = G.q2, e2 = G.e2, qe = G.qe, qe2 = G.qe2;
+	const int sc_mch = P.sc_mch, sc_mis = P.sc_mis, sc_N = G.sc_N;
 	const int n_strips = (tlen + ST_S - 1) / ST_S;
-	const bool exact = !(J.flag & 0x08);
-	const int qe_h = P.q + P.e;
+	const bool exact = !(J.flag & EZ_APPROX_MAX);
+	const int qe_h = G.qe_h;
 	const size_t Ld = (size_t)(qlen + tlen);
 	const int c0 = (int)k * ST_S, c1 = c0 + ST_S < tlen ? c0 + ST_S : tlen;
 	int n_col = qlen < tlen ? qlen : tlen;
@@ -84,24 +71,16 @@ void k_approx_strips(const DpJob *__restrict__ jobs, const uint32_t *__restrict_
 	uint32_t *keys = keys_all + (size_t)k * Ld;
 	int32_t *hen_arr = (int32_t*)(keys_all + (size_t)n_strips * Ld), *hst_arr = hen_arr + Ld;
 	uint32_t *hb_all = (uint32_t*)(hst_arr + Ld);
-	auto target_at = [&](int i) -> int { return i < tlen ? (int)bases.at(t_base + (uint64_t)(J.seq_rev ? tlen - 1 - i : i)) : 0; };
-	auto query_at = [&](int j) -> int {
-		if (j < 0 || j >= qlen) return 0;
-		const int pj = J.qs + (J.seq_rev ? qlen - 1 - j : j);
-		if (!J.q_rev) return bases.at(q_base + (uint64_t)(pj));
-		const int c = bases.at(q_base + (uint64_t)(J.qlen_full - 1 - pj));
-		return c < 4 ? 3 - c : 4;
-	};
 	for (int t = tid; t < ST_S + 16; t += ST_NTL) {
 		s_u[t] = s_y[t] = (int8_t)(-q - e); s_y2[t] = (int8_t)(-q2 - e2);
 		s_x[0][t] = s_x[1][t] = s_v[0][t] = s_v[1][t] = (int8_t)(-q - e);
 		s_x2[0][t] = s_x2[1][t] = (int8_t)(-q2 - e2);
-		s_t[t] = (uint8_t)target_at(c0 + t);
+		s_t[t] = (uint8_t)SV.target(c0 + t);
 		s_H[t] = KSW_NEG_INF;
 	}
 	if (tid == 0) s_hen = KSW_NEG_INF;
 	if (tid < 4) s_late[tid] = 0;
-	for (int p = tid; p < qlen + 64; p += ST_NTL) { const int j = qlen - 1 - (p - 32); s_q[p] = (j >= 0 && j < qlen) ? (uint8_t)query_at(j) : (uint8_t)0; }
+	for (int p = tid; p < qlen + 64; p += ST_NTL) { const int j = qlen - 1 - (p - 32); s_q[p] = (j >= 0 && j < qlen) ? (uint8_t)SV.query(j) : (uint8_t)0; }
 	__syncthreads();
 
 	const s2_t ZERO = splat2(0), ONE = splat2(1), MCH = splat2(sc_mch), Q1 = splat2(q), Q2 = splat2(q2), QE = splat2(qe), QE2 = splat2(qe2);
@@ -124,7 +103,7 @@ void k_approx_strips(const DpJob *__restrict__ jobs, const uint32_t *__restrict_
 	__syncthreads();
 	for (int r = r_first; r <= r_last; ++r) {
 		int st0, en0;
-		st_range(r, qlen, tlen, st0, en0);
+		diag_range(r, qlen, tlen, st0, en0);
 		const int lo = st0 > c0 ? st0 : c0, hi = en0 < c1 - 1 ? en0 : c1 - 1;
 		const int8_t *xr = s_x[r & 1], *vr = s_v[r & 1], *x2r = s_x2[r & 1];
 		int8_t *xw = s_x[(r + 1) & 1], *vw = s_v[(r + 1) & 1], *x2w = s_x2[(r + 1) & 1];
@@ -147,12 +126,12 @@ void k_approx_strips(const DpJob *__restrict__ jobs, const uint32_t *__restrict_
 		int x1, v1, x21;
 		if (c0 == 0) {
 			x1 = -q - e, x21 = -q2 - e2;
-			v1 = r == 0 ? -q - e : r < long_thres ? -e : r == long_thres ? long_diff : -e2;
+			v1 = G.first_row(r);
 		} else {
 			const uint32_t nb = s_bnd[it & 15];                // = bnd_in[r - 1]
 			x1 = (int)(int8_t)(nb & 0xff), v1 = (int)(int8_t)(nb >> 8 & 0xff), x21 = (int)(int8_t)(nb >> 16 & 0xff);
 		}
-		const int u_join = r == 0 ? -q - e : r < long_thres ? -e : r == long_thres ? long_diff : -e2;      // first-row u of column r
+		const int u_join = G.first_row(r);      // first-row u of column r
 		const int off_r = 32 + qlen - 1 - r;
 		const int st = st0 / 16 * 16;
 		uint8_t *prow = pmat + (size_t)r * n_col - st;
@@ -277,7 +256,6 @@ void k_approx_strips(const DpJob *__restrict__ jobs, const uint32_t *__restrict_
 	if (s_last + 1 != (uint32_t)n_strips) return;
 	__threadfence();
 	if (wave != 0) return;
-	int n_cigar = 0;
 	int bi = tlen - 1, bj = qlen - 1;
 	int ez_max = 0, ez_max_t = -1, ez_max_q = -1, ez_mqe = KSW_NEG_INF, ez_mqe_t = -1, ez_mte = KSW_NEG_INF, ez_mte_q = -1, zdropped = 0;
 	if (exact) {
@@ -290,7 +268,7 @@ void k_approx_strips(const DpJob *__restrict__ jobs, const uint32_t *__restrict_
 			const int r = r0 + lane;
 			unsigned long long best = 0; int hen = KSW_NEG_INF, hst = KSW_NEG_INF;
 			if (r < n_diag) {
-				int st0, en0; st_range(r, qlen, tlen, st0, en0);
+				int st0, en0; diag_range(r, qlen, tlen, st0, en0);
 				for (int kk = 0; kk < n_strips; ++kk) {
 					const int c0k = kk * ST_S, c1k = c0k + ST_S < tlen ? c0k + ST_S : tlen;
 					if (c0k <= en0 && c1k - 1 >= st0) {
@@ -311,7 +289,7 @@ void k_approx_strips(const DpJob *__restrict__ jobs, const uint32_t *__restrict_
 				const int mH = __builtin_amdgcn_readlane(mH_l, ii), mt = __builtin_amdgcn_readlane(mt_l, ii);
 				const int he = __builtin_amdgcn_readlane(hen, ii), hs = __builtin_amdgcn_readlane(hst, ii);
 				sat |= __builtin_amdgcn_readlane(sat_l, ii);
-				int st0, en0; st_range(rr, qlen, tlen, st0, en0);
+				int st0, en0; diag_range(rr, qlen, tlen, st0, en0);
 				if (en0 == tlen - 1 && he > ez_mte) ez_mte = he, ez_mte_q = rr - en0;
 				if (rr - st0 == qlen - 1 && hs > ez_mqe) ez_mqe = hs, ez_mqe_t = st0;
 				if (mH > ez_max) ez_max = mH, ez_max_t = mt, ez_max_q = rr - mt;
@@ -327,63 +305,14 @@ void k_approx_strips(const DpJob *__restrict__ jobs, const uint32_t *__restrict_
 		}
 		if (zdropped) bi = ez_max_t, bj = ez_max_q;
 	}
-	int i = bi, j = bj, state = 0; long long guard = 0;
-	uint32_t last_op = 0xffffffffu;
-	uint32_t run_len = 0;                               // the operation being extended lives in registers: one store per operation, not a
-	auto cg_push = [&](uint32_t op, uint32_t len) {     // read-modify-write of device memory per path step
-		if (op == last_op) { run_len += len; return; }
-		if (last_op != 0xffffffffu) { if (lane == 0) cig_tmp[n_cigar] = run_len << 4 | last_op; ++n_cigar; }
-		last_op = op; run_len = len;
-	};
-	auto cg_flush = [&] { if (last_op != 0xffffffffu && n_cigar >= 0) { if (lane == 0) cig_tmp[n_cigar] = run_len << 4 | last_op; ++n_cigar; last_op = 0xffffffffu; } };
-	while (i >= 0 && j >= 0) {
-		if (++guard > 4000000) { n_cigar = -7; break; }
-		const int r_hi = i + j, c_lo = i - (ST_BT - 1);
-		{
-			// all 64 rows of the window are requested before the first one is stored (a load-store pair per row would pay the memory
-			// latency 64 times per window, and a 10 kb x 10 kb path crosses ~300 windows)
-			uint8_t wv[ST_BT];
-#pragma unroll
-			for (int row = 0; row < ST_BT; ++row) {
-				const int r = r_hi - row, col = c_lo + lane;
-				uint8_t val = 0;
-				if (r >= 0 && col >= 0) {
-					int st0, en0; st_range(r, qlen, tlen, st0, en0);
-					const int off = st0 / 16 * 16;
-					if (st0 <= en0 && col >= st0 && col <= en0) val = pmat[(size_t)r * n_col + (col - off)];
-				}
-				wv[row] = val;
-			}
-#pragma unroll
-			for (int row = 0; row < ST_BT; ++row) s_win[row * ST_BT + lane] = wv[row];
-		}
-		__builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
-		while (i >= 0 && j >= 0) {
-			const int r = i + j, row = r_hi - r;
-			if (row >= ST_BT || i < c_lo) break;
-			int st0, en0; st_range(r, qlen, tlen, st0, en0);
-			const int off = st0 / 16 * 16, off_end = (en0 + 16) / 16 * 16 - 1;
-			int force_state = -1;
-			if (i < off) force_state = 2;
-			if (i > off_end) force_state = 1;
-			const uint32_t tmp = force_state < 0 ? s_win[row * ST_BT + (i - c_lo)] : 0;
-			if (state == 0) state = tmp & 7;
-			else if (!(tmp >> (state + 2) & 1)) state = 0;
-			if (state == 0) state = tmp & 7;
-			if (force_state >= 0) state = force_state;
-			uint32_t op;
-			if (state == 0) op = 0, --i, --j;
-			else if (state == 1 || state == 3) op = 2, --i;
-			else op = 1, --j;
-			cg_push(op, 1u);
-		}
-		__builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
-	}
-	if (bi >= 0 && bj >= 0 && n_cigar >= 0) {
-		if (i >= 0) cg_push(2u, (uint32_t)(i + 1));
-		if (j >= 0) cg_push(1u, (uint32_t)(j + 1));
-	}
-	cg_flush();
+	long long guard = 0;
+	// (this class stores a cell inside [st0, en0] proper, has no reversed CIGARs, and scores the path between the walk and the hand-over)
+	const int n_cigar = backtrack_windowed<BT_WIN, false>(lane, bi, bj, s_win, cig_tmp, guard, 4000000,
+		[&](int r, int &st0, int &en0) { diag_range(r, qlen, tlen, st0, en0); },
+		[&](int r, int col) -> uint8_t {
+			int st0, en0; diag_range(r, qlen, tlen, st0, en0);
+			return st0 <= en0 && col >= st0 && col <= en0 ? pmat[(size_t)r * n_col + (col - st0 / 16 * 16)] : (uint8_t)0;
+		});
 	__builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
 	// score of the path: cig_tmp runs from the end of the alignment to its start
 	int score = KSW_NEG_INF;
@@ -397,7 +326,7 @@ void k_approx_strips(const DpJob *__restrict__ jobs, const uint32_t *__restrict_
 				for (int b = 0; b < len; b += 64) {
 					const int l = b + lane;
 					bool mis = false, amb = false;
-					if (l < len) { const int x = target_at(ti + l), y = query_at(qj + l); amb = ((x | y) & 4) != 0; mis = !amb && x != y; }
+					if (l < len) { const int x = SV.target(ti + l), y = SV.query(qj + l); amb = ((x | y) & 4) != 0; mis = !amb && x != y; }
 					n_mis += __popcll(__ballot(mis)); n_amb += __popcll(__ballot(amb));
 				}
 				score += sc_mch * (len - n_mis - n_amb) + sc_mis * n_mis + sc_N * n_amb;
@@ -408,17 +337,9 @@ void k_approx_strips(const DpJob *__restrict__ jobs, const uint32_t *__restrict_
 			}
 		}
 	}
-	unsigned long long base = 0;
-	if (lane == 0 && n_cigar > 0) base = atomicAdd(pool_cursor, (unsigned long long)n_cigar);
-	base = ((unsigned long long)(unsigned)__shfl((int)(base >> 32), 0) << 32) | (unsigned)__shfl((int)(base & 0xffffffffULL), 0);
-	if (n_cigar > 0 && base + (unsigned long long)n_cigar <= pool_cap)
-		for (int c = lane; c < n_cigar; c += 64) cigar_pool[base + c] = cig_tmp[n_cigar - 1 - c];
-	if (lane == 0) {
-		DpRes R;
-		R.max = ez_max, R.max_q = ez_max_q, R.max_t = ez_max_t, R.mqe = ez_mqe, R.mqe_t = ez_mqe_t, R.mte = ez_mte, R.mte_q = ez_mte_q;
-		R.score = score, R.zdropped = zdropped, R.reach_end = 0, R.n_cigar = n_cigar, R.pad = qlen + tlen - 1, R.cigar_off = base;
-		res[jl] = R;
-	}
+	DpRes R = ez_record(ez_max, ez_max_q, ez_max_t, ez_mqe, ez_mqe_t, ez_mte, ez_mte_q, score, zdropped, 0);
+	R.n_cigar = n_cigar, R.pad = qlen + tlen - 1;
+	cigar_commit<false, true>(lane, n_cigar, false, cig_tmp, cigar_pool, pool_cursor, pool_cap, R, &res[jl]);
 }
 
 bool strips_eligible(const DpJob &j, const DpParams &P)
@@ -427,7 +348,7 @@ bool strips_eligible(const DpJob &j, const DpParams &P)
 	static const int min_x = getenv("PGA_STRIPS_EXACT_MIN") ? atoi(getenv("PGA_STRIPS_EXACT_MIN")) : 4096;   // exact second passes (every diagonal is computed, no early exit on z-drop): from 6 kb
 	if (min_t <= 0) return false;
 	if (!(j.w >= j.qlen && j.w >= j.tlen && j.qlen >= 256 && j.qlen + 64 <= ST_QMAX && P.sc_mch >= 0 && P.sc_mch < 127)) return false;
-	if (j.flag == 0x08) return j.tlen >= min_t;
+	if (j.flag == EZ_APPROX_MAX) return j.tlen >= min_t;
 	return j.flag == 0 && min_x > 0 && j.tlen >= min_x && (j.tlen + ST_S - 1) / ST_S <= 32 && (j.tlen % ST_S) != 1;
 }
 size_t strips_slab_bytes(const DpJob &j)
@@ -440,7 +361,7 @@ int strips_count(const DpJob &j) { return (j.tlen + ST_S - 1) / ST_S; }
 size_t strips_bnd_words(const DpJob &j)
 {
 	const size_t L = (size_t)(j.qlen + j.tlen), ns = (size_t)strips_count(j);
-	return (ns > 1 ? ns - 1 : 0) * L + ((j.flag & 0x08) ? 0 : ns * L + 2 * L + ns + 8);      // exact mode: keys, H of the first / last column per diagonal, hand-off words
+	return (ns > 1 ? ns - 1 : 0) * L + ((j.flag & EZ_APPROX_MAX) ? 0 : ns * L + 2 * L + ns + 8);      // exact mode: keys, H of the first / last column per diagonal, hand-off words
 }
 
 void launch_approx_strips(unsigned n_blocks, const DpJob *jobs, const uint32_t *blk_job, const uint32_t *blk_strip, PkBases bases, const DpParams &P, uint8_t *slab, const uint64_t *slab_off,

@@ -15,35 +15,13 @@
 //   * 3 workgroup barriers per diagonal (5 in exact-max mode); the exact maximum with the reference's tie order
 //     is a wave reduction + 4 LDS partials;
 //   * wave 0 walks the direction matrix back through a 64x64 LDS window (fences only, as in the fast kernel).
-#include <mutex>
 #include "pga_common.h"
-#include "pga_dp.h"
-#include "pga_wave.h"
+#include "pga_ksw_shared.h"
 #include <cstdio>
 #include "pga_pk16.h"
 
 namespace pga {
 
-#define KSW_NEG_INF (-0x40000000)
-#define EZ_RIGHT      0x02
-#define EZ_APPROX_MAX 0x08
-#define EZ_APPROX_DROP 0x10
-#define EZ_EXTZ_ONLY  0x40
-#define EZ_REV_CIGAR  0x80
-#define WBT 64
-#define WIDE_LDS_MAX (152 * 1024)   // dynamic LDS the kernel may ask for (160 KB per CU minus its static arrays); pga_ksw.hip sizes classes with it
-
-__device__ __forceinline__ int sx8w(int v) { return __builtin_amdgcn_sbfe(v, 0, 8); }
-
-__device__ __forceinline__ void diag_range_w(int r, int qlen, int tlen, int w, int &st0, int &en0)
-{
-	int st = 0, en = tlen - 1;
-	if (st < r - qlen + 1) st = r - qlen + 1;
-	if (en > r) en = r;
-	if (st < (r - w + 1) >> 1) st = (r - w + 1) >> 1;
-	if (en > (r + w) >> 1) en = (r + w) >> 1;
-	st0 = st, en0 = en;
-}
 
 __device__ int g_wide_no_fused = 0;   // PGA_NO_FUSED_APPROX=1 (A/B): the unbanded approximate passes take the general loop
 
@@ -59,17 +37,12 @@ void k_extd2_wide(const DpJob *__restrict__ jobs, uint32_t n_jobs, PkBases bases
 	__shared__ int s_hprev;
 	__shared__ int s_h0v[2], s_h0u[2];   // fused approximate path: v of the tracked column and u of its right neighbour, by diagonal parity
 	__builtin_amdgcn_s_setprio(3);      // few, latency-bound workgroups: win issue arbitration against the tile kernels sharing the CU
-	__shared__ uint8_t s_win[WBT * WBT];
+	__shared__ uint8_t s_win[BT_WIN * BT_WIN];
 	const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
 	uint8_t *slab = slab_all + (size_t)blockIdx.x * slab_bytes;
-	int q = P.q, e = P.e, q2 = P.q2, e2 = P.e2;
-	const int qe_h = q + e;
-	if (q2 + e2 < q + e) { int t = q; q = q2, q2 = t, t = e, e = e2, e2 = t; }
-	const int qe = q + e, qe2 = q2 + e2;
-	const int sc_mch = P.sc_mch, sc_mis = P.sc_mis, sc_N = P.sc_ambi == 0 ? -e2 : P.sc_ambi;
-	int long_thres = e != e2 ? (q2 - q) / (e - e2) - 1 : 0;
-	if (q2 + e2 + long_thres * e2 > q + e + long_thres * e) ++long_thres;
-	const int long_diff = long_thres * (e - e2) - (q2 - q) - e2;
+	const GapCosts G(P);
+	const int q = G.q, e = G.e, q2 = G.q2, e2 = G.e2, qe_h = G.qe_h, qe = G.qe, qe2 = G.qe2;
+	const int sc_mch = P.sc_mch, sc_mis = P.sc_mis, sc_N = G.sc_N;
 
 	for (;;) {
 		__syncthreads();
@@ -78,7 +51,7 @@ void k_extd2_wide(const DpJob *__restrict__ jobs, uint32_t n_jobs, PkBases bases
 		const uint32_t jid = s_job;
 		if (jid >= n_jobs) break;
 		const DpJob J = jobs[jid];
-		const uint64_t t_base = J.t_off, q_base = J.q_off;          // base positions in the packed store
+		const SeqView SV(bases, J);
 		const int qlen = J.qlen, tlen = J.tlen, flag = J.flag, zdrop = J.zdrop, end_bonus = J.end_bonus;
 		const bool approx_max = flag & EZ_APPROX_MAX, right = flag & EZ_RIGHT;
 		int w = J.w;
@@ -86,14 +59,6 @@ void k_extd2_wide(const DpJob *__restrict__ jobs, uint32_t n_jobs, PkBases bases
 		const int T = (tlen + 15) / 16 * 16;
 		int n_col = qlen < tlen ? qlen : tlen;
 		n_col = (((n_col < w + 1 ? n_col : w + 1) + 15) / 16 + 1) * 16;
-		auto target_at = [&](int i) -> int { return i < tlen ? (int)bases.at(t_base + (uint64_t)(J.seq_rev ? tlen - 1 - i : i)) : 0; };
-		auto query_at = [&](int j) -> int {
-			if (j < 0 || j >= qlen) return 0;
-			int pj = J.qs + (J.seq_rev ? qlen - 1 - j : j);
-			if (!J.q_rev) return bases.at(q_base + (uint64_t)(pj));
-			int c = bases.at(q_base + (uint64_t)(J.qlen_full - 1 - pj));
-			return c < 4 ? 3 - c : 4;
-		};
 		// LDS rows: ring of R columns (R == T when the whole target fits the launch's ring capacity)
 		int R = ((w < tlen ? w : tlen) + 15) / 16 * 16 + 96;
 		if (R > T) R = T;
@@ -115,10 +80,10 @@ void k_extd2_wide(const DpJob *__restrict__ jobs, uint32_t n_jobs, PkBases bases
 		const bool packed_ok = !right && w >= qlen && w >= tlen && R == T && sc_mch >= 0 && sc_mch < 127;
 		const bool swar_profile = packed_ok && seq_lds;     // query stored REVERSED with 32 zero bytes on either side: column t of diagonal r reads qq[t + 32+qlen-1-r]
 		if (seq_lds) {
-			for (int i = tid; i < seq_cap; i += WIDE_NT) tq[i] = i < tlen ? (uint8_t)target_at(i) : (uint8_t)0;
+			for (int i = tid; i < seq_cap; i += WIDE_NT) tq[i] = i < tlen ? (uint8_t)SV.target(i) : (uint8_t)0;
 			if (swar_profile) {
-				for (int p = tid; p < seq_cap + 64; p += WIDE_NT) { const int j = qlen - 1 - (p - 32); qq[p] = (j >= 0 && j < qlen) ? (uint8_t)query_at(j) : (uint8_t)0; }
-			} else for (int j = tid; j < qlen; j += WIDE_NT) qq[j] = (uint8_t)query_at(j);
+				for (int p = tid; p < seq_cap + 64; p += WIDE_NT) { const int j = qlen - 1 - (p - 32); qq[p] = (j >= 0 && j < qlen) ? (uint8_t)SV.query(j) : (uint8_t)0; }
+			} else for (int j = tid; j < qlen; j += WIDE_NT) qq[j] = (uint8_t)SV.query(j);
 		}
 		int init_hi = R - 1;                               // highest column whose slot holds that column's state
 		int ez_max = 0, ez_max_q = -1, ez_max_t = -1, ez_mqe = KSW_NEG_INF, ez_mqe_t = -1, ez_mte = KSW_NEG_INF, ez_mte_q = -1;
@@ -142,19 +107,19 @@ void k_extd2_wide(const DpJob *__restrict__ jobs, uint32_t n_jobs, PkBases bases
 			for (int r = 0; r < n_diag; ++r) {
 				r_done = r + 1;
 				int st0, en0;
-				diag_range_w(r, qlen, tlen, w, st0, en0);
+				diag_range(r, qlen, tlen, w, st0, en0);
 				const int st = st0 / 16 * 16, en = (en0 + 16) / 16 * 16 - 1;
 				const int8_t *xr = xb[r & 1], *vr = vb[r & 1], *x2r = x2b[r & 1];
 				int8_t *xw = xb[(r + 1) & 1], *vw = vb[(r + 1) & 1], *x2w = x2b[(r + 1) & 1];
 				int x1, x21, v1;
 				if (st > 0) {
 					if (st - 1 >= last_st && st - 1 <= last_en) { x1 = xr[st - 1], x21 = x2r[st - 1], v1 = vr[st - 1]; }
-					else x1 = sx8w(-q - e), x21 = sx8w(-q2 - e2), v1 = sx8w(-q - e);
+					else x1 = sx8(-q - e), x21 = sx8(-q2 - e2), v1 = sx8(-q - e);
 				} else {
-					x1 = sx8w(-q - e), x21 = sx8w(-q2 - e2);
-					v1 = r == 0 ? sx8w(-q - e) : r < long_thres ? sx8w(-e) : r == long_thres ? sx8w(long_diff) : sx8w(-e2);
+					x1 = sx8(-q - e), x21 = sx8(-q2 - e2);
+					v1 = sx8(G.first_row(r));
 				}
-				const int u_join = r == 0 ? -q - e : r < long_thres ? -e : r == long_thres ? long_diff : -e2;   // first-row u of column r
+				const int u_join = G.first_row(r);   // first-row u of column r
 				const int off_r = 32 + qlen - 1 - r;
 				const int h0t = r == 0 ? 0 : last_H0_t;
 				uint8_t *prow = pmat + (size_t)r * n_col - st;
@@ -213,7 +178,7 @@ void k_extd2_wide(const DpJob *__restrict__ jobs, uint32_t n_jobs, PkBases bases
 			r_done = r + 1;
 			if (pend_slot >= 0) { if (tid == 0) H[pend_slot] = pend_val; pend_slot = -1; }   // last diagonal's H[en0] (nobody reads H before two more barriers)
 			int st0, en0;
-			diag_range_w(r, qlen, tlen, w, st0, en0);
+			diag_range(r, qlen, tlen, w, st0, en0);
 			if (st0 > en0) { ez_zdropped = 1; break; }
 			const int st = st0 / 16 * 16, en = (en0 + 16) / 16 * 16 - 1;
 			while (st - 16 >= base + R) base += R;
@@ -240,15 +205,15 @@ void k_extd2_wide(const DpJob *__restrict__ jobs, uint32_t n_jobs, PkBases bases
 			int x1, x21, v1;
 			if (st > 0) {
 				if (st - 1 >= last_st && st - 1 <= last_en) { const int k = sl(st - 1); x1 = xr[k], x21 = x2r[k], v1 = vr[k]; }
-				else x1 = sx8w(-q - e), x21 = sx8w(-q2 - e2), v1 = sx8w(-q - e);
+				else x1 = sx8(-q - e), x21 = sx8(-q2 - e2), v1 = sx8(-q - e);
 			} else {
-				x1 = sx8w(-q - e), x21 = sx8w(-q2 - e2);
-				v1 = r == 0 ? sx8w(-q - e) : r < long_thres ? sx8w(-e) : r == long_thres ? sx8w(long_diff) : sx8w(-e2);
+				x1 = sx8(-q - e), x21 = sx8(-q2 - e2);
+				v1 = sx8(G.first_row(r));
 			}
 			if (en >= r && tid == 0) {
 				const int k = sl(r);
 				y[k] = (int8_t)(-q - e), y2[k] = (int8_t)(-q2 - e2);
-				u[k] = (int8_t)(r == 0 ? -q - e : r < long_thres ? -e : r == long_thres ? long_diff : -e2);
+				u[k] = (int8_t)G.first_row(r);
 			}
 			if (swar_profile) {
 				// four columns per thread and iteration on 32-bit words: equal bytes <=> zero bytes of a ^ b (all values <= 4, so +0x7f sets
@@ -271,7 +236,7 @@ void k_extd2_wide(const DpJob *__restrict__ jobs, uint32_t n_jobs, PkBases bases
 				if (t < T) {
 					int a, b;
 					if (seq_lds) { a = t < tlen ? (int)tq[t] : 0; const int j = r - t; b = (j >= 0 && j < qlen) ? (int)qq[j] : 0; }
-					else a = target_at(t), b = query_at(r - t);
+					else a = SV.target(t), b = SV.query(r - t);
 					int sc = a == b ? sc_mch : sc_mis;
 					if (a == 4 || b == 4) sc = sc_N;
 					s[sl(t)] = (int8_t)sc;
@@ -318,7 +283,7 @@ void k_extd2_wide(const DpJob *__restrict__ jobs, uint32_t n_jobs, PkBases bases
 				const int xt1 = t == st ? x1 : (int)xr[k1], vt1 = t == st ? v1 : (int)vr[k1], x2t1 = t == st ? x21 : (int)x2r[k1];
 				const int ut = u[k], yo = y[k], y2o = y2[k];
 				int z = s[k];
-				int a = sx8w(xt1 + vt1), b = sx8w(yo + ut), a2 = sx8w(x2t1 + vt1), b2 = sx8w(y2o + ut), d;
+				int a = sx8(xt1 + vt1), b = sx8(yo + ut), a2 = sx8(x2t1 + vt1), b2 = sx8(y2o + ut), d;
 				if (!right) {
 					d = 0;
 					if (a > z) d = 1, z = a;
@@ -333,8 +298,8 @@ void k_extd2_wide(const DpJob *__restrict__ jobs, uint32_t n_jobs, PkBases bases
 				}
 				if (sc_mch < z) z = sc_mch;
 				u[k] = (int8_t)(z - vt1), vw[k] = (int8_t)(z - ut);
-				int tmp = sx8w(z - q); a = sx8w(a - tmp), b = sx8w(b - tmp);
-				tmp = sx8w(z - q2); a2 = sx8w(a2 - tmp), b2 = sx8w(b2 - tmp);
+				int tmp = sx8(z - q); a = sx8(a - tmp), b = sx8(b - tmp);
+				tmp = sx8(z - q2); a2 = sx8(a2 - tmp), b2 = sx8(b2 - tmp);
 				if (!right) {
 					xw[k]  = (int8_t)((a  > 0 ? a  : 0) - qe);  if (a  > 0) d |= 0x08;
 					y[k]   = (int8_t)((b  > 0 ? b  : 0) - qe);  if (b  > 0) d |= 0x10;
@@ -418,82 +383,24 @@ void k_extd2_wide(const DpJob *__restrict__ jobs, uint32_t n_jobs, PkBases bases
 		}
 
 		// ---- backtrack by wave 0 (ksw2.h:127-159), LDS window, fences only ----
-		int n_cigar = 0, bi = -1, bj = -1;
+		int bi = -1, bj = -1;
 		if (!ez_zdropped && !(flag & EZ_EXTZ_ONLY)) bi = tlen - 1, bj = qlen - 1;
 		else if (!ez_zdropped && (flag & EZ_EXTZ_ONLY) && ez_mqe + end_bonus > ez_max) ez_reach_end = 1, bi = ez_mqe_t, bj = qlen - 1;
 		else if (ez_max_t >= 0 && ez_max_q >= 0) bi = ez_max_t, bj = ez_max_q;
 		__threadfence_block();
 		__syncthreads();
 		if (wave == 0) {
-			int i = bi, j = bj, state = 0; long long guard = 0;
-			uint32_t last_op = 0xffffffffu;
-			uint32_t run_len = 0;                               // the operation being extended lives in registers: one store per operation, not a
-			auto cg_push = [&](uint32_t op, uint32_t len) {     // read-modify-write of device memory per path step
-				if (op == last_op) { run_len += len; return; }
-				if (last_op != 0xffffffffu) { if (lane == 0) cig_tmp[n_cigar] = run_len << 4 | last_op; ++n_cigar; }
-				last_op = op; run_len = len;
-			};
-			auto cg_flush = [&] { if (last_op != 0xffffffffu && n_cigar >= 0) { if (lane == 0) cig_tmp[n_cigar] = run_len << 4 | last_op; ++n_cigar; last_op = 0xffffffffu; } };
-			while (i >= 0 && j >= 0) {
-				if (++guard > 4000000) { n_cigar = -7; break; }
-				const int r_hi = i + j, c_lo = i - (WBT - 1);
-				{
-					// all 64 rows of the window are requested before the first one is stored: 64 loads in flight instead of 64 round trips
-					uint8_t wv[WBT];
-#pragma unroll
-					for (int row = 0; row < WBT; ++row) {
-						const int r = r_hi - row, col = c_lo + lane;
-						uint8_t val = 0;
-						if (r >= 0 && col >= 0) {
-							int st0, en0; diag_range_w(r, qlen, tlen, w, st0, en0);
-							const int off = st0 / 16 * 16, off_end = (en0 + 16) / 16 * 16 - 1;
-							if (st0 <= en0 && col >= off && col <= off_end) val = pmat[(size_t)r * n_col + (col - off)];
-						}
-						wv[row] = val;
-					}
-#pragma unroll
-					for (int row = 0; row < WBT; ++row) s_win[row * WBT + lane] = wv[row];
-				}
-				__builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
-				while (i >= 0 && j >= 0) {
-					const int r = i + j, row = r_hi - r;
-					if (row >= WBT || i < c_lo) break;
-					int st0, en0; diag_range_w(r, qlen, tlen, w, st0, en0);
+			long long guard = 0;
+			const int n_cigar = backtrack_windowed<BT_WIN, false>(lane, bi, bj, s_win, cig_tmp, guard, 4000000,
+				[&](int r, int &st0, int &en0) { diag_range(r, qlen, tlen, w, st0, en0); },
+				[&](int r, int col) -> uint8_t {                       // stored: the sixteen-rounded range
+					int st0, en0; diag_range(r, qlen, tlen, w, st0, en0);
 					const int off = st0 / 16 * 16, off_end = (en0 + 16) / 16 * 16 - 1;
-					int force_state = -1;
-					if (i < off) force_state = 2;
-					if (i > off_end) force_state = 1;
-					const uint32_t tmp = force_state < 0 ? s_win[row * WBT + (i - c_lo)] : 0;
-					if (state == 0) state = tmp & 7;
-					else if (!(tmp >> (state + 2) & 1)) state = 0;
-					if (state == 0) state = tmp & 7;
-					if (force_state >= 0) state = force_state;
-					uint32_t op;
-					if (state == 0) op = 0, --i, --j;
-					else if (state == 1 || state == 3) op = 2, --i;
-					else op = 1, --j;
-					cg_push(op, 1u);
-				}
-				__builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
-			}
-			if (bi >= 0 && bj >= 0 && n_cigar >= 0) {
-				if (i >= 0) cg_push(2u, (uint32_t)(i + 1));
-				if (j >= 0) cg_push(1u, (uint32_t)(j + 1));
-			}
-			cg_flush();
-			unsigned long long base = 0;
-			if (lane == 0 && n_cigar > 0) base = atomicAdd(pool_cursor, (unsigned long long)n_cigar);
-			base = ((unsigned long long)(unsigned)__shfl((int)(base >> 32), 0) << 32) | (unsigned)__shfl((int)(base & 0xffffffffULL), 0);
-			__builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
-			const bool rev_cigar = flag & EZ_REV_CIGAR;
-			if (n_cigar > 0 && base + (unsigned long long)n_cigar <= pool_cap)
-				for (int c = lane; c < n_cigar; c += 64) cigar_pool[base + c] = rev_cigar ? cig_tmp[c] : cig_tmp[n_cigar - 1 - c];
-			if (lane == 0) {
-				DpRes R;
-				R.max = ez_max, R.max_q = ez_max_q, R.max_t = ez_max_t, R.mqe = ez_mqe, R.mqe_t = ez_mqe_t, R.mte = ez_mte, R.mte_q = ez_mte_q;
-				R.score = ez_score, R.zdropped = ez_zdropped, R.reach_end = ez_reach_end, R.n_cigar = n_cigar, R.pad = r_done, R.cigar_off = base;
-				res[jid] = R;
-			}
+					return st0 <= en0 && col >= off && col <= off_end ? pmat[(size_t)r * n_col + (col - off)] : (uint8_t)0;
+				});
+			DpRes R = ez_record(ez_max, ez_max_q, ez_max_t, ez_mqe, ez_mqe_t, ez_mte, ez_mte_q, ez_score, ez_zdropped, ez_reach_end);
+			R.n_cigar = n_cigar, R.pad = r_done;
+			cigar_commit<true, true>(lane, n_cigar, flag & EZ_REV_CIGAR, cig_tmp, cigar_pool, pool_cursor, pool_cap, R, &res[jid]);
 		}
 	}
 }
@@ -503,12 +410,7 @@ size_t wide_lds_bytes(int r_cap, int seq_cap, bool exact) { return (size_t)r_cap
 template <int NT> static void launch_wide_nt(unsigned n_blocks, size_t lds, hipStream_t st, const DpJob *jobs, uint32_t n_jobs, PkBases bases, const DpParams &P, uint32_t *counter, uint8_t *slab,
                                              size_t slab_bytes, int r_cap, int seq_cap, int exact, DpRes *res, uint32_t *pool, unsigned long long *cursor, unsigned long long pool_cap)
 {
-	{	// a per-DEVICE function attribute, set once per device whatever thread comes first
-		static std::mutex mu; static bool attr_set[64] = {};
-		int dev = 0; PGA_HIP(hipGetDevice(&dev));
-		std::lock_guard<std::mutex> lk(mu);
-		if (!attr_set[dev & 63]) { PGA_HIP(hipFuncSetAttribute((const void*)k_extd2_wide<NT>, hipFuncAttributeMaxDynamicSharedMemorySize, WIDE_LDS_MAX)); attr_set[dev & 63] = true; }
-	}
+	set_max_dynamic_lds_once((const void*)k_extd2_wide<NT>, WIDE_LDS_MAX);
 	hipLaunchKernelGGL(k_extd2_wide<NT>, dim3(n_blocks), dim3(NT), lds, st, jobs, n_jobs, bases, P, counter, slab, slab_bytes, r_cap, seq_cap, exact, res, pool, cursor, pool_cap);
 }
 

@@ -16,21 +16,13 @@
 // end-of-sequence decisions in order (ksw2_extd2_sse.c:326-366, ksw2.h:167-184).  No int8 wrap can occur inside an unbinding band, so the
 // difference recurrence runs in plain 32-bit integers.
 #include "pga_common.h"
-#include "pga_dp.h"
-#include "pga_wave.h"
+#include "pga_ksw_shared.h"
 #include <cstring>
 
 namespace pga {
 
-#define KSW_NEG_INF (-0x40000000)
 #define WS_W 64             // columns per strip = lanes
-#define WS_BT 64
 
-__device__ __forceinline__ void ws_range(int r, int qlen, int tlen, int &st0, int &en0)
-{
-	st0 = r - qlen + 1 > 0 ? r - qlen + 1 : 0;
-	en0 = r < tlen - 1 ? r : tlen - 1;
-}
 __device__ __forceinline__ int ws_sx8(uint32_t v, int sh) { return __builtin_amdgcn_sbfe((int)v, sh, 8); }
 __device__ __forceinline__ unsigned long long ws_readlane64(unsigned long long v, int l)
 {
@@ -44,16 +36,12 @@ __device__ __forceinline__ void wstrip_body(const DpJob &J, const uint32_t jl, c
                uint32_t *__restrict__ done_ctr, DpRes *__restrict__ res, uint32_t *__restrict__ cigar_pool, unsigned long long *__restrict__ pool_cursor, unsigned long long pool_cap)
 {
 	const int lane = threadIdx.x;
-	const uint64_t t_base = J.t_off, q_base = J.q_off;
+	const SeqView SV(bases, J);
 	const int qlen = J.qlen, tlen = J.tlen;
-	int q = P.q, e = P.e, q2 = P.q2, e2 = P.e2;
-	if (q2 + e2 < q + e) { int t = q; q = q2, q2 = t, t = e, e = e2, e2 = t; }
-	const int qe = q + e, qe2 = q2 + e2;
-	const int sc_mch = P.sc_mch, sc_mis = P.sc_mis, sc_N = P.sc_ambi == 0 ? -e2 : P.sc_ambi;
-	int long_thres = e != e2 ? (q2 - q) / (e - e2) - 1 : 0;
-	if (q2 + e2 + long_thres * e2 > q + e + long_thres * e) ++long_thres;
-	const int long_diff = long_thres * (e - e2) - (q2 - q) - e2;
-	const int qe_h = P.q + P.e;
+	const GapCosts G(P);
+	const int q = G.q, e = G.e, q2 = G.q2, e2 = G.e2, qe = G.qe, qe2 = G.qe2;
+	const int sc_mch = P.sc_mch, sc_mis = P.sc_mis, sc_N = G.sc_N;
+	const int qe_h = G.qe_h;
 	const int n_strips = (tlen + WS_W - 1) / WS_W;
 	const size_t Ld = (size_t)(qlen + tlen);
 	const int c0 = (int)k * WS_W, c1 = c0 + WS_W < tlen ? c0 + WS_W : tlen;
@@ -66,21 +54,13 @@ __device__ __forceinline__ void wstrip_body(const DpJob &J, const uint32_t jl, c
 	unsigned long long *bnd_out = (int)k + 1 < n_strips ? bnd + (size_t)k * Ld : nullptr;
 	// exact mode, behind the boundary words: H of the diagonal's last and first column per diagonal, then the best key of every diagonal
 	int32_t *hen_arr = (int32_t*)(bnd + (size_t)(n_strips > 1 ? n_strips - 1 : 0) * Ld), *hst_arr = hen_arr + Ld;
-	auto target_at = [&](int i) -> int { return (i >= 0 && i < tlen) ? (int)bases.at(t_base + (uint64_t)(J.seq_rev ? tlen - 1 - i : i)) : 0; };
-	auto query_at = [&](int j) -> int {
-		if (j < 0 || j >= qlen) return 0;
-		const int pj = J.qs + (J.seq_rev ? qlen - 1 - j : j);
-		if (!J.q_rev) return bases.at(q_base + (uint64_t)(pj));
-		const int c = bases.at(q_base + (uint64_t)(J.qlen_full - 1 - pj));
-		return c < 4 ? 3 - c : 4;
-	};
 	const int t = c0 + lane;
 	const bool has_col = t < tlen;
-	const int tb = target_at(t);
+	const int tb = SV.target_any(t);
 	// The lane's column: what its last cell left behind (ksw2's rows at index t): u, y, y2 as integers, x, v, x2 as the bytes of one word (the
 	// word the lane on the right takes by DPP).  A column joins the matrix on diagonal r = t with the first-row values: y, y2 are the rows'
 	// initial values anyway and u's first-row value only depends on t, so the registers simply start there and the loop knows no "join".
-	const int u_first = t == 0 ? -q - e : t < long_thres ? -e : t == long_thres ? long_diff : -e2;
+	const int u_first = G.first_row(t);
 	int U = u_first, Y = -q - e, Y2 = -q2 - e2, H = KSW_NEG_INF;
 	uint32_t PK = ((uint32_t)(-q - e) & 0xffu) | ((uint32_t)(-q - e) & 0xffu) << 8 | ((uint32_t)(-q2 - e2) & 0xffu) << 16;
 	int qb = 0;
@@ -92,10 +72,10 @@ __device__ __forceinline__ void wstrip_body(const DpJob &J, const uint32_t jl, c
 	unsigned long long *best_arr = (unsigned long long*)(hst_arr + Ld);   // exact mode: the best key of every diagonal over all strips
 	int jq = -lane - 1;                                          // query row of the lane's cell on the diagonal BEFORE the block's first: r - t
 	uint8_t *prow = pmat + (size_t)r_first * n_col;              // row of the direction matrix of the current diagonal, minus its first column st(r)
-	{ int st0, en0; ws_range(r_first, qlen, tlen, st0, en0); prow -= st0 / 16 * 16; }
+	{ int st0, en0; diag_range(r_first, qlen, tlen, st0, en0); prow -= st0 / 16 * 16; }
 	for (int it0 = 0; r_first + it0 <= r_last; it0 += 64) {
 		// the block's inputs: 64 query bases (diagonal r = r_first + it brings base it to lane 0) and 64 boundary words
-		const int qwin = query_at(it0 + lane);
+		const int qwin = SV.query(it0 + lane);
 		unsigned long long inw = 0;
 		{
 			const int d = r_first - 1 + it0 + lane;               // the cell of diagonal d + 1 in column c0 reads the left strip's state after diagonal d
@@ -104,7 +84,7 @@ __device__ __forceinline__ void wstrip_body(const DpJob &J, const uint32_t jl, c
 					for (;;) { inw = __hip_atomic_load(&bnd_in[d], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); if (inw >> 31 & 1ULL) break; __builtin_amdgcn_s_sleep(2); }
 			} else {
 				// the matrix's first column: x, x2 of a fresh gap, v the first-column value of row d + 1 (ksw2_extd2_sse.c:191-194); no H to its left
-				const int rr = d + 1, v1 = rr == 0 ? -q - e : rr < long_thres ? -e : rr == long_thres ? long_diff : -e2;
+				const int rr = d + 1, v1 = G.first_row(rr);
 				inw = (unsigned long long)(uint32_t)KSW_NEG_INF << 32 | (((uint32_t)(-q - e) & 0xffu) | ((uint32_t)v1 & 0xffu) << 8 | ((uint32_t)(-q2 - e2) & 0xffu) << 16);
 			}
 		}
@@ -142,7 +122,7 @@ __device__ __forceinline__ void wstrip_body(const DpJob &J, const uint32_t jl, c
 				// H[t] += v[t] over [st0, en0); H[en0] = H[en0-1] (as the previous diagonal left it) + u[en0]; the maximum with the reference's tie order
 				// (H[en0] first, then four lanes by (t - st0) & 3 over [st0, en1), then the tail) is one key per column
 				int st0, en0;
-				ws_range(r, qlen, tlen, st0, en0);
+				diag_range(r, qlen, tlen, st0, en0);
 				uint32_t key = 0;
 				if (active) {
 					const int en1 = st0 + (en0 - st0) / 4 * 4;
@@ -190,7 +170,6 @@ __device__ __forceinline__ void wstrip_body(const DpJob &J, const uint32_t jl, c
 	last = (uint32_t)__builtin_amdgcn_readfirstlane((int)last);
 	if (last + 1 != (uint32_t)n_strips) return;
 	__threadfence();
-	int n_cigar = 0;
 	int bi = tlen - 1, bj = qlen - 1;
 	int ez_max = 0, ez_max_t = -1, ez_max_q = -1, ez_mqe = KSW_NEG_INF, ez_mqe_t = -1, ez_mte = KSW_NEG_INF, ez_mte_q = -1, zdropped = 0;
 	if (EXACT) {
@@ -203,7 +182,7 @@ __device__ __forceinline__ void wstrip_body(const DpJob &J, const uint32_t jl, c
 			const int r = r0 + lane;
 			unsigned long long best = 0; int hen = KSW_NEG_INF, hst = KSW_NEG_INF;
 			if (r < n_diag) {
-				int st0, en0; ws_range(r, qlen, tlen, st0, en0);
+				int st0, en0; diag_range(r, qlen, tlen, st0, en0);
 				best = best_arr[r];
 				hen = hen_arr[r];
 				if (r - st0 == qlen - 1) hst = hst_arr[r];
@@ -217,7 +196,7 @@ __device__ __forceinline__ void wstrip_body(const DpJob &J, const uint32_t jl, c
 				const int mH = __builtin_amdgcn_readlane(mH_l, ii), mt = __builtin_amdgcn_readlane(mt_l, ii);
 				const int he = __builtin_amdgcn_readlane(hen, ii), hs = __builtin_amdgcn_readlane(hst, ii);
 				sat |= __builtin_amdgcn_readlane(sat_l, ii);
-				int st0, en0; ws_range(rr, qlen, tlen, st0, en0);
+				int st0, en0; diag_range(rr, qlen, tlen, st0, en0);
 				if (en0 == tlen - 1 && he > ez_mte) ez_mte = he, ez_mte_q = rr - en0;
 				if (rr - st0 == qlen - 1 && hs > ez_mqe) ez_mqe = hs, ez_mqe_t = st0;
 				if (mH > ez_max) ez_max = mH, ez_max_t = mt, ez_max_q = rr - mt;
@@ -233,61 +212,14 @@ __device__ __forceinline__ void wstrip_body(const DpJob &J, const uint32_t jl, c
 		}
 		if (zdropped) bi = ez_max_t, bj = ez_max_q;
 	}
-	int i = bi, j = bj, state = 0; long long guard = 0;
-	uint32_t last_op = 0xffffffffu;
-	uint32_t run_len = 0;
-	auto cg_push = [&](uint32_t op, uint32_t len) {
-		if (op == last_op) { run_len += len; return; }
-		if (last_op != 0xffffffffu) { if (lane == 0) cig_tmp[n_cigar] = run_len << 4 | last_op; ++n_cigar; }
-		last_op = op; run_len = len;
-	};
-	auto cg_flush = [&] { if (last_op != 0xffffffffu && n_cigar >= 0) { if (lane == 0) cig_tmp[n_cigar] = run_len << 4 | last_op; ++n_cigar; last_op = 0xffffffffu; } };
-	while (i >= 0 && j >= 0) {
-		if (++guard > 4000000) { n_cigar = -7; break; }
-		const int r_hi = i + j, c_lo = i - (WS_BT - 1);
-		{
-			uint8_t wv[WS_BT];
-#pragma unroll
-			for (int row = 0; row < WS_BT; ++row) {
-				const int r = r_hi - row, col = c_lo + lane;
-				uint8_t val = 0;
-				if (r >= 0 && col >= 0) {
-					int st0, en0; ws_range(r, qlen, tlen, st0, en0);
-					const int off = st0 / 16 * 16;
-					if (st0 <= en0 && col >= st0 && col <= en0) val = pmat[(size_t)r * n_col + (col - off)];
-				}
-				wv[row] = val;
-			}
-#pragma unroll
-			for (int row = 0; row < WS_BT; ++row) s_win[row * WS_BT + lane] = wv[row];
-		}
-		__builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
-		while (i >= 0 && j >= 0) {
-			const int r = i + j, row = r_hi - r;
-			if (row >= WS_BT || i < c_lo) break;
-			int st0, en0; ws_range(r, qlen, tlen, st0, en0);
-			const int off = st0 / 16 * 16, off_end = (en0 + 16) / 16 * 16 - 1;
-			int force_state = -1;
-			if (i < off) force_state = 2;
-			if (i > off_end) force_state = 1;
-			const uint32_t tmp = force_state < 0 ? s_win[row * WS_BT + (i - c_lo)] : 0;
-			if (state == 0) state = tmp & 7;
-			else if (!(tmp >> (state + 2) & 1)) state = 0;
-			if (state == 0) state = tmp & 7;
-			if (force_state >= 0) state = force_state;
-			uint32_t op;
-			if (state == 0) op = 0, --i, --j;
-			else if (state == 1 || state == 3) op = 2, --i;
-			else op = 1, --j;
-			cg_push(op, 1u);
-		}
-		__builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
-	}
-	if (bi >= 0 && bj >= 0 && n_cigar >= 0) {
-		if (i >= 0) cg_push(2u, (uint32_t)(i + 1));
-		if (j >= 0) cg_push(1u, (uint32_t)(j + 1));
-	}
-	cg_flush();
+	long long guard = 0;
+	// (this class stores a cell inside [st0, en0] proper, has no reversed CIGARs, and scores the path between the walk and the hand-over)
+	const int n_cigar = backtrack_windowed<BT_WIN, false>(lane, bi, bj, s_win, cig_tmp, guard, 4000000,
+		[&](int r, int &st0, int &en0) { diag_range(r, qlen, tlen, st0, en0); },
+		[&](int r, int col) -> uint8_t {
+			int st0, en0; diag_range(r, qlen, tlen, st0, en0);
+			return st0 <= en0 && col >= st0 && col <= en0 ? pmat[(size_t)r * n_col + (col - st0 / 16 * 16)] : (uint8_t)0;
+		});
 	__builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
 	// score of the path: cig_tmp runs from the end of the alignment to its start
 	int score = KSW_NEG_INF;
@@ -301,7 +233,7 @@ __device__ __forceinline__ void wstrip_body(const DpJob &J, const uint32_t jl, c
 				for (int b = 0; b < len; b += 64) {
 					const int l = b + lane;
 					bool mis = false, amb = false;
-					if (l < len) { const int x = target_at(ti + l), y = query_at(qj + l); amb = ((x | y) & 4) != 0; mis = !amb && x != y; }
+					if (l < len) { const int x = SV.target_any(ti + l), y = SV.query(qj + l); amb = ((x | y) & 4) != 0; mis = !amb && x != y; }
 					n_mis += __popcll(__ballot(mis)); n_amb += __popcll(__ballot(amb));
 				}
 				score += sc_mch * (len - n_mis - n_amb) + sc_mis * n_mis + sc_N * n_amb;
@@ -312,17 +244,9 @@ __device__ __forceinline__ void wstrip_body(const DpJob &J, const uint32_t jl, c
 			}
 		}
 	}
-	unsigned long long base = 0;
-	if (lane == 0 && n_cigar > 0) base = atomicAdd(pool_cursor, (unsigned long long)n_cigar);
-	base = ((unsigned long long)(unsigned)__shfl((int)(base >> 32), 0) << 32) | (unsigned)__shfl((int)(base & 0xffffffffULL), 0);
-	if (n_cigar > 0 && base + (unsigned long long)n_cigar <= pool_cap)
-		for (int c = lane; c < n_cigar; c += 64) cigar_pool[base + c] = cig_tmp[n_cigar - 1 - c];
-	if (lane == 0) {
-		DpRes R;
-		R.max = ez_max, R.max_q = ez_max_q, R.max_t = ez_max_t, R.mqe = ez_mqe, R.mqe_t = ez_mqe_t, R.mte = ez_mte, R.mte_q = ez_mte_q;
-		R.score = score, R.zdropped = zdropped, R.reach_end = 0, R.n_cigar = n_cigar, R.pad = qlen + tlen - 1, R.cigar_off = base;
-		res[jl] = R;
-	}
+	DpRes R = ez_record(ez_max, ez_max_q, ez_max_t, ez_mqe, ez_mqe_t, ez_mte, ez_mte_q, score, zdropped, 0);
+	R.n_cigar = n_cigar, R.pad = qlen + tlen - 1;
+	cigar_commit<false, true>(lane, n_cigar, false, cig_tmp, cigar_pool, pool_cursor, pool_cap, R, &res[jl]);
 }
 
 __global__ __launch_bounds__(64)
@@ -333,7 +257,7 @@ void k_wstrips(const DpJob *__restrict__ jobs, const uint32_t *__restrict__ blk_
 	__shared__ __align__(16) uint8_t s_win[64 * 65 * 4];      // traceback window (64 x 64 bytes); exact mode, before that: the keys of a block
 	const uint32_t jl = blk_job[blockIdx.x], k = blk_strip[blockIdx.x];
 	const DpJob J = jobs[jl];
-	if (J.flag & 0x08) wstrip_body<false>(J, jl, k, s_win, bases, P, slab_all, slab_off, bnd_all, bnd_off, done_ctr, res, cigar_pool, pool_cursor, pool_cap);
+	if (J.flag & EZ_APPROX_MAX) wstrip_body<false>(J, jl, k, s_win, bases, P, slab_all, slab_off, bnd_all, bnd_off, done_ctr, res, cigar_pool, pool_cursor, pool_cap);
 	else wstrip_body<true>(J, jl, k, s_win, bases, P, slab_all, slab_off, bnd_all, bnd_off, done_ctr, res, cigar_pool, pool_cursor, pool_cap);
 }
 
@@ -344,14 +268,14 @@ bool wstrips_eligible(const DpJob &j, const DpParams &P)
 	static const int min_x = getenv("PGA_WSTRIPS_EXACT_MIN") ? atoi(getenv("PGA_WSTRIPS_EXACT_MIN")) : 2048;
 	if (min_t <= 0) return false;
 	if (!(j.w >= j.qlen && j.w >= j.tlen && j.qlen >= 256 && j.qlen <= 16384 && j.tlen <= 16384 && P.sc_mch >= 0 && P.sc_mch < 127)) return false;
-	if (j.flag == 0x08) return j.tlen >= min_t;
+	if (j.flag == EZ_APPROX_MAX) return j.tlen >= min_t;
 	return j.flag == 0 && min_x > 0 && j.tlen >= min_x;
 }
 int wstrips_count(const DpJob &j) { return (j.tlen + WS_W - 1) / WS_W; }
 size_t wstrips_bnd_words(const DpJob &j)          // 64-bit words
 {
 	const size_t L = (size_t)(j.qlen + j.tlen), ns = (size_t)wstrips_count(j);
-	return (ns > 1 ? ns - 1 : 0) * L + ((j.flag & 0x08) ? 0 : (2 * L + 1) / 2 + 1 + L) + 8;      // exact: hen, hst (32 bit), best key per diagonal (64 bit)
+	return (ns > 1 ? ns - 1 : 0) * L + ((j.flag & EZ_APPROX_MAX) ? 0 : (2 * L + 1) / 2 + 1 + L) + 8;      // exact: hen, hst (32 bit), best key per diagonal (64 bit)
 }
 
 void launch_wstrips(unsigned n_blocks, const DpJob *jobs, const uint32_t *blk_job, const uint32_t *blk_strip, PkBases bases, const DpParams &P, uint8_t *slab,

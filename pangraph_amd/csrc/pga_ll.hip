@@ -17,9 +17,8 @@
 // replaces read five int16 values per cell from LDS and took 2.3 us per diagonal of a 10 kb x 10 kb problem; this one 1.0 us per
 // column step).  Scores are int32 here; they never leave the int16 range for the sizes accepted (the launcher checks
 // a * qlen < 32000), so the reference's saturating arithmetic is the plain one.
-#include <mutex>
 #include "pga_common.h"
-#include "pga_dp.h"
+#include "pga_ksw_shared.h"
 #include "pga_wave.h"
 
 namespace pga {
@@ -48,27 +47,21 @@ void k_ll_i16(const DpJob *__restrict__ jobs, uint32_t n_jobs, PkBases bases, Dp
 		const uint32_t jid = s_job;
 		if (jid >= n_jobs) break;
 		const DpJob J = jobs[jid];
-		const uint64_t t_base = J.t_off, q_base = J.q_off;          // base positions in the packed store
+		const SeqView SV(bases, J);
 		const int qlen = J.qlen, tlen = J.tlen;
 		const int slen = (qlen + 7) / 8, qlen8 = slen * 8;
 		const int R = (tlen + LL_NT - 1) / LL_NT;              // rows per thread (uniform)
 		const int n_act = (tlen + R - 1) / R;                  // threads that own at least one row
 		const int i0 = tid * R;
 		for (int j = tid; j < qlen8; j += LL_NT) {
-			int c = 4;
-			if (j < qlen) {
-				const int pj = J.qs + (J.seq_rev ? qlen - 1 - j : j);
-				if (!J.q_rev) c = bases.at(q_base + (uint64_t)(pj));
-				else { c = bases.at(q_base + (uint64_t)(J.qlen_full - 1 - pj)); c = c < 4 ? 3 - c : 4; }
-			}
-			qb[j] = (uint8_t)(j < qlen ? c : 5);                // 5: padding column, score 0
+			qb[j] = (uint8_t)(j < qlen ? SV.query_in(j) : 5);                // 5: padding column, score 0
 		}
 		// this thread's rows: target base, and the mismatch score it pays (N rows pay the ambiguity score against everything)
 		int ta[LL_RMAX], tm[LL_RMAX], Hl[LL_RMAX], Fl[LL_RMAX];
 #pragma unroll
 		for (int k = 0; k < LL_RMAX; ++k) {
 			const int i = i0 + k;
-			const int a = (k < R && i < tlen) ? (int)bases.at(t_base + (uint64_t)(J.seq_rev ? tlen - 1 - i : i)) : 4;
+			const int a = (k < R && i < tlen) ? SV.target_in(i) : 4;   // (rows beyond the target are padded with 4, not 0)
 			ta[k] = a; tm[k] = a == 4 ? sc_N : sc_mis; Hl[k] = 0; Fl[k] = 0;
 		}
 		if (tid < 2 * (LL_NT / 64)) { (&s_xh[0][0])[tid] = 0; (&s_xe[0][0])[tid] = 0; }
@@ -169,7 +162,7 @@ void k_ll_multi(const DpJob *__restrict__ jobs, uint32_t n_jobs, int G, PkBases 
 	const int gapoe = P.q + P.e, ge = P.e;
 	const int sc_mch = P.sc_mch, sc_mis = P.sc_mis, sc_N = P.sc_ambi;
 	const DpJob J = jobs[jid];
-	const uint64_t t_base = J.t_off, q_base = J.q_off;
+	const SeqView SV(bases, J);
 	const int qlen = J.qlen, tlen = J.tlen;
 	const int slen = (qlen + 7) / 8, qlen8 = slen * 8;
 	const int R = (tlen + G * NT - 1) / (G * NT);      // rows per thread (uniform over the problem)
@@ -183,19 +176,13 @@ void k_ll_multi(const DpJob *__restrict__ jobs, uint32_t n_jobs, int G, PkBases 
 	if (n_act > 0) {
 		const int i0 = (g * NT + tid) * R;
 		for (int j = tid; j < qlen8; j += NT) {
-			int c = 4;
-			if (j < qlen) {
-				const int pj = J.qs + (J.seq_rev ? qlen - 1 - j : j);
-				if (!J.q_rev) c = bases.at(q_base + (uint64_t)(pj));
-				else { c = bases.at(q_base + (uint64_t)(J.qlen_full - 1 - pj)); c = c < 4 ? 3 - c : 4; }
-			}
-			qb[j] = (uint8_t)(j < qlen ? c : 5);
+			qb[j] = (uint8_t)(j < qlen ? SV.query_in(j) : 5);
 		}
 		int ta[LL_RMAX], tm[LL_RMAX], Hl[LL_RMAX], Fl[LL_RMAX];
 #pragma unroll
 		for (int k = 0; k < LL_RMAX; ++k) {
 			const int i = i0 + k;
-			const int a = (k < R && i < tlen) ? (int)bases.at(t_base + (uint64_t)(J.seq_rev ? tlen - 1 - i : i)) : 4;
+			const int a = (k < R && i < tlen) ? SV.target_in(i) : 4;   // (rows beyond the target are padded with 4, not 0)
 			ta[k] = a; tm[k] = a == 4 ? sc_N : sc_mis; Hl[k] = 0; Fl[k] = 0;
 		}
 		if (tid < 2 * (NT / 64)) { (&s_xh[0][0])[tid] = 0; (&s_xe[0][0])[tid] = 0; }
@@ -319,12 +306,7 @@ int ll_groups(uint32_t n_jobs, int t_max)
 
 template <int NT> static void launch_ll_multi_nt(int G, int t_cap, const DpJob *jobs, uint32_t n_jobs, PkBases bases, const DpParams &P, unsigned long long *scratch, DpRes *res, hipStream_t st)
 {
-	{
-		static std::mutex mu; static bool attr_set[64] = {};
-		int dev = 0; PGA_HIP(hipGetDevice(&dev));
-		std::lock_guard<std::mutex> lk(mu);
-		if (!attr_set[dev & 63]) { PGA_HIP(hipFuncSetAttribute((const void*)k_ll_multi<NT>, hipFuncAttributeMaxDynamicSharedMemorySize, 152 * 1024)); attr_set[dev & 63] = true; }
-	}
+	set_max_dynamic_lds_once((const void*)k_ll_multi<NT>, 152 * 1024);
 	hipLaunchKernelGGL(k_ll_multi<NT>, dim3(n_jobs * (unsigned)G), dim3(NT), ll_lds_bytes(t_cap), st, jobs, n_jobs, G, bases, P, scratch, res);
 }
 void launch_ll_multi(int G, int t_cap, const DpJob *jobs, uint32_t n_jobs, PkBases bases, const DpParams &P, unsigned long long *scratch, DpRes *res, hipStream_t st)
@@ -339,12 +321,7 @@ void launch_ll_multi(int G, int t_cap, const DpJob *jobs, uint32_t n_jobs, PkBas
 void launch_ll_i16(unsigned n_blocks, int t_cap, const DpJob *jobs, uint32_t n_jobs, PkBases bases, const DpParams &P, uint32_t *counter,
                    unsigned long long *rowkey, size_t rowkey_stride, DpRes *res, hipStream_t st)
 {
-	{	// a per-DEVICE function attribute, set once per device whatever thread comes first
-		static std::mutex mu; static bool attr_set[64] = {};
-		int dev = 0; PGA_HIP(hipGetDevice(&dev));
-		std::lock_guard<std::mutex> lk(mu);
-		if (!attr_set[dev & 63]) { PGA_HIP(hipFuncSetAttribute((const void*)k_ll_i16, hipFuncAttributeMaxDynamicSharedMemorySize, 152 * 1024)); attr_set[dev & 63] = true; }
-	}
+	set_max_dynamic_lds_once((const void*)k_ll_i16, 152 * 1024);
 	hipLaunchKernelGGL(k_ll_i16, dim3(n_blocks), dim3(LL_NT), ll_lds_bytes(t_cap), st, jobs, n_jobs, bases, P, counter, rowkey, rowkey_stride, t_cap, res);
 }
 

@@ -164,13 +164,9 @@ static void mash_sketch_all(const SeqSet &S, int k, int w, MashSketch &M, hipStr
 	DBuf<uint32_t> d_cnt(nc);
 	const bool small = 2 * k + 1 <= 32;
 	const size_t lds = (size_t)w * 64 * (small ? sizeof(uint32_t) : sizeof(uint64_t));
-	static bool attr = false;
-	if (!attr) {
-		for (const void *f : {(const void*)k_mash_chunks<0, uint64_t>, (const void*)k_mash_chunks<1, uint64_t>, (const void*)k_mash_chunks<2, uint64_t>,
-		                      (const void*)k_mash_chunks<0, uint32_t>, (const void*)k_mash_chunks<1, uint32_t>, (const void*)k_mash_chunks<2, uint32_t>})
-			PGA_HIP(hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, 255 * 64 * 8));
-		attr = true;
-	}
+	for (const void *f : {(const void*)k_mash_chunks<0, uint64_t>, (const void*)k_mash_chunks<1, uint64_t>, (const void*)k_mash_chunks<2, uint64_t>,
+	                      (const void*)k_mash_chunks<0, uint32_t>, (const void*)k_mash_chunks<1, uint32_t>, (const void*)k_mash_chunks<2, uint32_t>})
+		set_max_dynamic_lds_once(f, 255 * 64 * 8);
 	auto launch = [&](int mode, uint32_t *cnt, const uint64_t *off, uint64_t *val, uint64_t *pos, uint32_t cap) {
 		const dim3 g((nc + 63) / 64), b(64);
 #define PGA_MASH_GO(M, R) hipLaunchKernelGGL((k_mash_chunks<M, R>), g, b, lds, st, S.bases(), S.d_off.p, S.d_len.p, d_ch.p, nc, k, w, cnt, off, val, pos, cap)

@@ -25,8 +25,7 @@ __device__ __forceinline__ int post_qbase(PkBases bases, uint64_t q_off, int qle
 {
 	const int pj = q_start + j;
 	if (!q_rev) return bases.at(q_off + (uint64_t)pj);
-	const int c = bases.at(q_off + (uint64_t)(qlen_full - 1 - pj));
-	return c < 4 ? 3 - c : 4;
+	return PkBases::complement(bases.at(q_off + (uint64_t)(qlen_full - 1 - pj)));
 }
 
 __device__ __forceinline__ uint32_t wave_sum_u32(uint32_t v) { return (uint32_t)__builtin_amdgcn_readlane((int)wave_prefix_sum_incl(v), 63); }

@@ -142,5 +142,16 @@ __device__ __forceinline__ long long wave_max_i64(long long v)
 	const int lo = __builtin_amdgcn_readlane((int)(v & 0xffffffffLL), 63), hi = __builtin_amdgcn_readlane((int)(v >> 32), 63);
 	return ((long long)hi << 32) | (unsigned)lo;
 }
+// the same maximum as a butterfly of shuffles (what the single-wave DP kernels were built and measured with)
+__device__ __forceinline__ long long wave_max64(long long v)
+{
+#pragma unroll
+	for (int d = 32; d >= 1; d >>= 1) {
+		int lo = __shfl_xor((int)(v & 0xffffffffLL), d), hi = __shfl_xor((int)(v >> 32), d);
+		long long o = ((long long)hi << 32) | (unsigned int)lo;
+		v = o > v ? o : v;
+	}
+	return v;
+}
 
 } // namespace pga
