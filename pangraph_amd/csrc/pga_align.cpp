@@ -1,8 +1,8 @@
 // pga_align.cpp -- the base-level alignment DRIVER of a batch: control flow on the host, every byte of data work on the device.
 //
-// Replaces (reference: packages/minimap2-sys/minimap2/) hit.c's region bookkeeping (mm_gen_regs, mm_split_reg, mm_filter_regs,
-// mm_hit_sort, mm_set_mapq: hit.c:8-88,106-123,188-218,290-329,396-466) and align.c's mm_align_skeleton / mm_align1 /
-// mm_align1_inv with their helpers (align.c:355-509,575-1022).  The reference aligns one region after another and calls the DP
+// Replaces (reference: packages/minimap2-sys/minimap2/) align.c's mm_align_skeleton / mm_align1 / mm_align1_inv with their helpers
+// (align.c:355-509,575-1022); hit.c's region bookkeeping and the mapq arithmetic are in pga_regions.cpp, what the planner kernel computes
+// the same way in pga_plan.h.  The reference aligns one region after another and calls the DP
 // kernel, the z-drop test and the CIGAR post-processing synchronously, reading bases as it goes.  Here
 //   * every region of every query of the batch is a small STATE MACHINE over compact records (chain anchors, DP results):
 //       plan     what mm_align1 decides before its first DP call: trimmed ends, ignored seeds, DP windows, gap-fill segments
@@ -19,233 +19,23 @@
 #include "pga_dp.h"
 #include "pga_post.h"
 #include "pga_plan.h"
-#include "pga_sort_exact.h"
+#include "pga_regions.h"
 #include "pga_pipeline.h"
 #include <cmath>
 #include <thread>
 #include <atomic>
 #include <list>
-#include <condition_variable>
 #include <deque>
 #include <chrono>
 #include <cstdio>
-#include <mutex>
 #include <numeric>
 
 namespace pga {
 
 static inline double wall_s() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
 
-// anchor flag bits (mmpriv.h:18-24) and DP flags (ksw2.h:11-20)
-static const uint64_t A_LONG_JOIN = 1ULL << 40, A_IGNORE = 1ULL << 41, A_TANDEM = 1ULL << 42, A_SELF = 1ULL << 43;
+// DP flags (ksw2.h:11-20); the anchor flag bits and the view of a query's anchors: pga_plan.h
 static const int DP_NEG_INF = -0x40000000, DP_RIGHT = 0x02, DP_APPROX_MAX = 0x08, DP_EXTZ_ONLY = 0x40, DP_REV_CIGAR = 0x80;
-
-// ---- anchors of one query: x = strand<<63 | target<<32 | target position, y = flags | span<<32 | query position (lchain.c:140-147) ----
-struct Anchors {
-	u128 *a; int32_t n;
-	int32_t tpos(int i) const { return (int32_t)a[i].x; }
-	int32_t qpos(int i) const { return (int32_t)a[i].y; }
-	int32_t span(int i) const { return (int32_t)(a[i].y >> 32 & 0xff); }
-	uint64_t target_key(int i) const { return a[i].x >> 32; }        // strand + target id
-	bool flagged(int i, uint64_t f) const { return (a[i].y & f) != 0; }
-	void flag(int i, uint64_t f) { a[i].y |= f; }
-	// query advance minus target advance between anchor i-1 and i: > 0 insertion, < 0 deletion
-	int32_t indel(int i) const { return (qpos(i) - qpos(i - 1)) - (tpos(i) - tpos(i - 1)); }
-};
-
-static void sort_by_x(std::vector<u128> &v) { uint32_t head[256], tail[256]; if (!v.empty()) radix_sort_128x_exact(v.data(), v.data() + v.size(), head, tail); }
-
-// ---------------------------------------------------------------- region records from chains
-// Coordinates of a chain (hit.c:23-38) and its approximate match / block lengths (hit.c:8-21): one pass over the anchors.
-static void chain_extent(Reg &r, int32_t qlen, const Anchors &A)
-{
-	const int first = r.as, last = r.as + r.cnt - 1;
-	const int32_t sp0 = A.span(first);
-	r.rev = (uint32_t)(A.a[first].x >> 63);
-	r.rid = (int32_t)(A.a[first].x << 1 >> 33);
-	r.rs = std::max(0, A.tpos(first) + 1 - sp0);
-	r.re = A.tpos(last) + 1;
-	const int32_t q_lo = A.qpos(first) + 1 - sp0, q_hi = A.qpos(last) + 1;       // on the aligned strand
-	if (r.rev) r.qs = qlen - q_hi, r.qe = qlen - q_lo; else r.qs = q_lo, r.qe = q_hi;
-	int32_t covered = 0, block = 0;
-	if (r.cnt > 0) {
-		covered = block = sp0;
-		for (int i = first + 1; i <= last; ++i) {
-			const int32_t dt = A.tpos(i) - A.tpos(i - 1), dq = A.qpos(i) - A.qpos(i - 1), sp = A.span(i);
-			block += std::max(dt, dq);
-			covered += (dt > sp && dq > sp) ? sp : std::min(dt, dq);
-		}
-	}
-	r.mlen = covered, r.blen = block;
-}
-
-static inline uint64_t mix64(uint64_t k) // the 64-bit finalizer hit.c:40-50 salts region keys with
-{
-	k = ~k + (k << 21); k ^= k >> 24;
-	k = k + (k << 3) + (k << 8); k ^= k >> 14;
-	k = k + (k << 2) + (k << 4); k ^= k >> 28;
-	k += k << 31;
-	return k;
-}
-static inline uint32_t name_hash31(const std::string &s) { uint32_t h = 0; bool first = true; for (unsigned char c : s) { h = first ? c : h * 31u + c; first = false; } return h; }   // X31 string hash (khash.h)
-static inline uint32_t mix32(uint32_t k) { k += ~(k << 15); k ^= k >> 10; k += k << 3; k ^= k >> 6; k += ~(k << 11); k ^= k >> 16; return k; }   // Wang's 32-bit mix (map.c:246-248)
-
-// One region per chain, ordered by descending (score<<32 | cnt) ^ salt(first anchor, query) -- hit.c:52-88.  The order of equal keys
-// is the one minimap2's radix sort leaves, so the keys go through its exact replay.
-static void regions_from_chains(uint32_t query_salt, int qlen, int n_chains, const uint64_t *u, const Anchors &A, std::vector<Reg> &regs, const u128 *heads = nullptr)
-{
-	// heads: the first anchor of every chain, gathered on the device (then A holds no anchors and the extents are left to the planner)
-	regs.clear();
-	if (n_chains == 0) return;
-	std::vector<u128> key((size_t)n_chains);
-	int32_t start = 0;
-	for (int c = 0; c < n_chains; ++c) {
-		const u128 h0 = heads ? heads[c] : A.a[start];
-		const uint32_t salt = (uint32_t)mix64((mix64(h0.x) + mix64(h0.y)) ^ query_salt);
-		const int32_t cnt = (int32_t)u[c];
-		key[(size_t)c].x = u[c] ^ salt;
-		key[(size_t)c].y = (uint64_t)start << 32 | (uint32_t)cnt;
-		start += cnt;
-	}
-	sort_by_x(key);
-	regs.resize((size_t)n_chains);
-	for (int c = 0; c < n_chains; ++c) {
-		const u128 &k = key[(size_t)(n_chains - 1 - c)];          // descending
-		Reg &r = regs[(size_t)c] = Reg();
-		r.id = c, r.parent = -1;                                   // -X: no primary/secondary selection, parents stay unset
-		r.score = r.score0 = (int32_t)(k.x >> 32), r.hash = (uint32_t)k.x;
-		r.cnt = (int32_t)(uint32_t)k.y, r.as = (int32_t)(k.y >> 32);
-		if (!heads) chain_extent(r, qlen, A);
-	}
-}
-
-// The tail of `head` from its anchor `n_keep` on becomes its own region (hit.c:106-123); scores are shared out by anchor counts.
-static void cut_region(Reg &head, Reg &tail, int n_keep, int qlen, const Anchors &A, bool extents = true)
-{
-	if (n_keep <= 0 || n_keep >= head.cnt) return;
-	const int total = head.cnt;
-	tail = head;
-	tail.id = -1, tail.split_inv = 0;
-	tail.has_p = false, tail.cigar.clear(), tail.dp_score = tail.dp_max = tail.dp_max2 = 0, tail.n_ambi = 0;
-	tail.as = head.as + n_keep, tail.cnt = total - n_keep;
-	tail.score = (int32_t)(head.score * ((float)tail.cnt / total) + .499);
-	if (head.parent == head.id) tail.parent = -2;                 // MM_PARENT_TMP_PRI
-	head.cnt = n_keep, head.score -= tail.score;
-	// (device-side planning: the tail's extent comes back with its plan; the head's is overwritten by what its alignment found)
-	if (extents) { chain_extent(tail, qlen, A); chain_extent(head, qlen, A); }
-	head.split |= 1, tail.split |= 2;
-}
-
-static bool region_survives(const mm_mapopt_t &opt, int qlen, const Reg &r) // hit.c:290-309
-{
-	if (!r.inv && r.cnt < opt.min_cnt) return false;
-	if (!r.has_p) return true;
-	if (r.mlen < opt.min_chain_score || r.dp_max < opt.min_dp_max) return false;
-	return !(r.qs > qlen * opt.max_clip_ratio && qlen - r.qe > qlen * opt.max_clip_ratio);
-}
-static void drop_weak_regions(const mm_mapopt_t &opt, int qlen, std::vector<Reg> &regs)
-{
-	regs.erase(std::remove_if(regs.begin(), regs.end(), [&](const Reg &r) { return !region_survives(opt, qlen, r); }), regs.end());
-}
-
-// descending DP score (chain score without a CIGAR), ties by the salted hash, equal keys as minimap2's sort leaves them (hit.c:188-218)
-static void order_regions(std::vector<Reg> &regs)
-{
-	if (regs.size() <= 1) return;
-	std::vector<u128> key; key.reserve(regs.size());
-	for (size_t i = 0; i < regs.size(); ++i) {
-		const Reg &r = regs[i];
-		if (!r.inv && r.cnt <= 0) continue;
-		key.push_back(u128{(uint64_t)(r.has_p ? r.dp_max : r.score) << 32 | r.hash, (uint64_t)i});
-	}
-	sort_by_x(key);
-	std::vector<Reg> out; out.reserve(key.size());
-	for (auto it = key.rbegin(); it != key.rend(); ++it) out.push_back(std::move(regs[it->y]));
-	regs.swap(out);
-}
-
-// mapping quality of one primary region (hit.c:421-466, long reads); float arithmetic in the reference's order
-static uint32_t region_mapq(const Reg &r, float uniq_ratio, int min_chain_sc, int match_sc)
-{
-	const float coef = 40.0f;
-	const float by_score = (r.score > 100 ? 1.0f : 0.01f * r.score) * uniq_ratio, by_cnt = r.cnt > 10 ? 1.0f : 0.1f * r.cnt;
-	const float pen = by_score < by_cnt ? by_score : by_cnt;
-	const int subsc = std::max(r.subsc, min_chain_sc);
-	int mapq;
-	if (r.has_p && r.dp_max2 > 0 && r.dp_max > 0) {
-		const float identity = (float)r.mlen / r.blen;
-		const float x = (float)r.dp_max2 * subsc / r.dp_max / r.score0;
-		mapq = (int)(identity * pen * coef * (1.0f - x * x) * logf((float)r.dp_max / match_sc));
-		const int alt = (int)(6.02f * identity * identity * (r.dp_max - r.dp_max2) / match_sc + .499f);
-		mapq = std::min(mapq, alt);
-	} else {
-		const float x = (float)subsc / r.score0;
-		if (r.has_p) { const float identity = (float)r.mlen / r.blen; mapq = (int)(identity * pen * coef * (1.0f - x) * logf((float)r.dp_max / match_sc)); }
-		else mapq = (int)(pen * coef * (1.0f - x) * logf(r.score));
-	}
-	mapq -= (int)(4.343f * logf(r.n_sub + 1) + .499f);
-	uint32_t q = (uint32_t)std::min(60, std::max(0, mapq));
-	if (r.has_p && r.dp_max > r.dp_max2 && q == 0) q = 1;
-	return q;
-}
-static void assign_mapq(std::vector<Reg> &regs, int min_chain_sc, int match_sc, int rep_len)
-{
-	if (regs.empty()) return;
-	int64_t primary_sum = 0;
-	for (const Reg &r : regs) if (r.parent == r.id) primary_sum += r.score;
-	const float uniq_ratio = (float)primary_sum / (primary_sum + rep_len);
-	for (Reg &r : regs) r.mapq = (!r.inv && r.parent == r.id) ? region_mapq(r, uniq_ratio, min_chain_sc, match_sc) : 0;
-	// an inversion inherits the weaker of its two flanks (hit.c:396-419)
-	if (regs.size() < 3 || std::none_of(regs.begin(), regs.end(), [](const Reg &r) { return r.inv != 0; })) return;
-	std::vector<u128> by_pos;
-	for (int i = 0; i < (int)regs.size(); ++i) if (regs[(size_t)i].parent == i || regs[(size_t)i].parent < 0) by_pos.push_back(u128{(uint64_t)regs[(size_t)i].rid << 32 | (uint32_t)regs[(size_t)i].rs, (uint64_t)i});
-	sort_by_x(by_pos);
-	for (size_t i = 1; i + 1 < by_pos.size(); ++i) {
-		Reg &mid = regs[by_pos[i].y];
-		if (mid.inv) mid.mapq = std::min(regs[by_pos[i - 1].y].mapq, regs[by_pos[i + 1].y].mapq);
-	}
-}
-
-static inline float log2_approx(float x) // mmpriv.h:118-126 (valid for x >= 2)
-{
-	union { float f; uint32_t i; } z = { x };
-	float r = (float)(((z.i >> 23) & 255) - 128);
-	z.i &= ~(255u << 23);
-	z.i += 127u << 23;
-	r += (-0.34484843f * z.f + 2.02466578f) * z.f - 0.67487759f;
-	return r;
-}
-
-// Re-scale dp_max of all regions of a query by the divergence of its best one (align.c:897-960).  The operation lists supply the
-// gap lengths in order (the reference's double accumulation is order-bound).
-static void rescale_dp_max(int qlen, std::vector<Reg> &regs, float frac, int a, int b)
-{
-	if (regs.size() < 2) return;
-	int best = -1, top = -1, second = -1;
-	for (int i = 0; i < (int)regs.size(); ++i) {
-		const Reg &r = regs[(size_t)i];
-		if (!r.has_p) continue;
-		if (r.dp_max > top) second = top, top = r.dp_max, best = i;
-		else if (r.dp_max > second) second = r.dp_max;
-	}
-	if (best < 0 || top < 0 || second < 0) return;
-	const Reg &lead = regs[(size_t)best];
-	if (lead.qe - lead.qs < (double)qlen * frac || second < (double)top * frac) return;
-	int32_t n_open = 0, n_base = 0;
-	for (uint32_t c : lead.cigar) { const uint32_t op = c & 0xf; if (op == 1 || op == 2) ++n_open, n_base += (int32_t)(c >> 4); }
-	const double identity = (double)lead.mlen / (lead.blen + (int32_t)lead.n_ambi - n_base + n_open);     // mm_event_identity
-	double div = 1. - identity;
-	if (div < 0.02) div = 0.02;
-	double b2 = 0.5 / div;
-	if (b2 * a < b) b2 = (double)a / b;
-	for (Reg &r : regs) {
-		if (!r.has_p) continue;
-		double gap_cost = 0.0; int32_t gap_bases = 0;
-		for (uint32_t c : r.cigar) { const uint32_t op = c & 0xf; if (op == 1 || op == 2) { gap_cost += b2 + (double)log2_approx((float)(1.0 + (c >> 4))); gap_bases += (int32_t)(c >> 4); } }
-		const int32_t n_mis = r.blen + (int32_t)r.n_ambi - r.mlen - gap_bases;
-		r.dp_max = std::max(0, (int32_t)(a * (r.mlen - b2 * n_mis - gap_cost) + .499));
-	}
-}
 
 // ---------------------------------------------------------------- seeds of a chain that the DP must not trust (align.c:373-509)
 struct LongGaps { std::vector<int> at; };     // chain-relative indices i whose |indel(i)| exceeds a threshold; only used when there are >= 2
@@ -315,37 +105,20 @@ static void join_crowded_gaps(Anchors &A, int as1, int cnt1, int min_gap, int re
 	}
 }
 
-// Seeds at either end of a chain that sit off the diagonal of what follows are cut off (align.c:471-509).
-static void trim_chain_ends(const Reg &r, const Anchors &A, int bw, int min_match, int32_t &as1, int32_t &cnt1)
-{
-	as1 = r.as, cnt1 = r.cnt;
-	if (r.cnt < 3) return;
-	const int last = r.as + r.cnt - 1;
-	auto settled = [&](int32_t len, int32_t match) { return len >= bw << 1 || (match >= min_match && match >= bw) || match >= r.mlen >> 1; };
-	int32_t len, match;
-	len = match = A.span(r.as);
-	for (int i = r.as + 1; i < last; ++i) {
-		if (A.flagged(i, A_LONG_JOIN)) break;
-		const int32_t dt = A.tpos(i) - A.tpos(i - 1), dq = A.qpos(i) - A.qpos(i - 1), lo = std::min(dt, dq), hi = std::max(dt, dq);
-		if (hi - lo > len >> 1) as1 = i;
-		len += lo, match += std::min(lo, A.span(i));
-		if (settled(len, match)) break;
-	}
-	cnt1 = last + 1 - as1;
-	len = match = A.span(last);
-	for (int i = last - 1; i > as1; --i) {
-		if (A.flagged(i + 1, A_LONG_JOIN)) break;
-		const int32_t dt = A.tpos(i + 1) - A.tpos(i), dq = A.qpos(i + 1) - A.qpos(i), lo = std::min(dt, dq), hi = std::max(dt, dq);
-		if (hi - lo > len >> 1) cnt1 = i + 1 - as1;
-		len += lo, match += std::min(lo, A.span(i + 1));
-		if (settled(len, match)) break;
-	}
-}
+// (the end trimming, align.c:471-509, and the extension windows, align.c:633-696: pga_plan.h -- the planner kernel runs the same functions)
 
 static inline bool ll_on_device(const mm_mapopt_t &opt, int q_len, int t_len)
 {
 	const int q8 = (q_len + 7) / 8 * 8;
 	return q_len > 0 && t_len > 0 && q8 <= PGA_LL_MAX_LEN && t_len <= PGA_LL_MAX_LEN && (int64_t)std::abs(opt.a) * q8 < 32000;
+}
+// A local alignment (ksw_ll_i16) over windows the device kernel does not hold.  Unreachable from pangraph's options -- both windows are
+// bounded by max_gap = 10 000 under every asm preset (align.c:81-82, 845-855; PGA_LL_MAX_LEN = 10 240) -- so it is refused, loudly,
+// instead of being computed somewhere else: this library has no host path for base work.
+[[noreturn]] static void ll_window_too_long(int q_len, int t_len)
+{
+	throw std::runtime_error("pga: ksw_ll_i16 over windows of " + std::to_string(q_len) + " x " + std::to_string(t_len) + " bases: the device kernel holds " + std::to_string(PGA_LL_MAX_LEN) +
+	                         " (max_gap above 10000 is outside pangraph's presets)");
 }
 
 // A sufficient condition for mm_test_zdrop (align.c:47-89) to return 0 that needs no sequence: every z it tracks is at
@@ -547,7 +320,7 @@ struct Driver {
 		if (bw_long < bw) bw_long = bw;
 		T.bw = bw;
 		int32_t as1, cnt1, rs, qs, re, qe, rs0, qs0, re0, qe0, rs1, qs1, re1, qe1, i, l;
-		if (!(opt.flag & MM_F_NO_END_FLT)) trim_chain_ends(r, A, opt.bw, opt.min_chain_score * 2, as1, cnt1);
+		if (!(opt.flag & MM_F_NO_END_FLT)) trim_chain_ends(A, r.as, r.cnt, r.mlen, opt.bw, opt.min_chain_score * 2, as1, cnt1);
 		else as1 = r.as, cnt1 = r.cnt;
 		ignore_indel_bursts(A, as1, cnt1, 10, 40, opt.max_gap >> 1, 10);
 		join_crowded_gaps(A, as1, cnt1, 30, opt.max_gap >> 1);
@@ -563,15 +336,6 @@ struct Driver {
 				if (++l > opt.min_cnt) { l = std::max(rs0 - x, qs0 - y); rs1 = std::max(0, rs0 - l), qs1 = qs0 - l; break; }
 			}
 		}
-		if (qs > 0 && rs > 0) {
-			l = std::min(qs, opt.max_gap);
-			qs1 = std::max(qs1, qs - l);
-			qs0 = std::min(qs0, qs1);
-			l += l * opt.a > opt.q ? (l * opt.a - opt.q) / opt.e : 0;
-			l = std::min(std::min(l, opt.max_gap), rs);
-			rs1 = std::max(rs1, rs - l);
-			rs0 = std::min(std::min(rs0, rs1), rs);
-		} else rs0 = rs, qs0 = qs;
 		re0 = A.tpos(r.as + r.cnt - 1) + 1, qe0 = A.qpos(r.as + r.cnt - 1) + 1;
 		re1 = tlen_ref, qe1 = qlen;
 		for (i = r.as + r.cnt, l = 0; i < A.n && A.target_key(i) == A.target_key(r.as); ++i) {
@@ -580,23 +344,7 @@ struct Driver {
 				if (++l > opt.min_cnt) { l = std::max(x - re0, y - qe0); re1 = re0 + l, qe1 = qe0 + l; break; }
 			}
 		}
-		if (qe < qlen && re < tlen_ref) {
-			l = std::min(qlen - qe, opt.max_gap);
-			qe1 = std::min(qe1, qe + l);
-			qe0 = std::max(qe0, qe1);
-			l += l * opt.a > opt.q ? (l * opt.a - opt.q) / opt.e : 0;
-			l = std::min(std::min(l, opt.max_gap), tlen_ref - re);
-			re1 = std::min(re1, re + l);
-			re0 = std::max(re0, re1);
-		} else re0 = re, qe0 = qe;
-		if (A.flagged(r.as, A_SELF)) {
-			int max_ext = std::abs(r.qs - r.rs);
-			if (r.rs - rs0 > max_ext) rs0 = r.rs - max_ext;
-			if (r.qs - qs0 > max_ext) qs0 = r.qs - max_ext;
-			max_ext = std::abs(r.qe - r.re);
-			if (re0 - r.re > max_ext) re0 = r.re + max_ext;
-			if (qe0 - r.qe > max_ext) qe0 = r.qe + max_ext;
-		}
+		extension_windows(rs, qs, re, qe, rs0, qs0, re0, qe0, rs1, qs1, re1, qe1, qlen, tlen_ref, A.flagged(r.as, A_SELF), r.rs, r.qs, r.re, r.qe, opt.max_gap, opt.a, opt.q, opt.e);
 		T.as1 = as1, T.cnt1 = cnt1, T.rs = rs, T.qs = qs, T.rs0 = rs0, T.qs0 = qs0, T.re0 = re0, T.qe0 = qe0;
 		// left extension (align.c:702-722): reversed windows, right-aligned gaps, reversed CIGAR
 		if (qs > 0 && rs > 0)
@@ -635,15 +383,6 @@ struct Driver {
 
 	int second_pass(QueryCtx &Q, const RegTask &T, const Seg &sg, int zdrop) { return request(Q, T.rev, T.rid, sg.qs, sg.qe - sg.qs, sg.rs, sg.re - sg.rs, 0, sg.bw1, -1, zdrop, 0); }
 	int zcode_of(const Seg &sg, int ll_score) const { return (ll_score >= opt.min_chain_score * opt.a && ll_score >= opt.min_dp_max) ? 2 : (sg.max_zdrop > opt.zdrop ? 1 : 0); }
-
-	// A local alignment (ksw_ll_i16) over windows the device kernel does not hold.  Unreachable from pangraph's options -- both windows are
-	// bounded by max_gap = 10 000 under every asm preset (align.c:81-82, 845-855; PGA_LL_MAX_LEN = 10 240) -- so it is refused, loudly,
-	// instead of being computed somewhere else: this library has no host path for base work.
-	int ll_on_host(QueryCtx &, int, int32_t, int q_len, int, int32_t, int t_len, bool, int *, int *)
-	{
-		throw std::runtime_error("pga: ksw_ll_i16 over windows of " + std::to_string(q_len) + " x " + std::to_string(t_len) + " bases: the device kernel holds " + std::to_string(PGA_LL_MAX_LEN) +
-		                         " (max_gap above 10000 is outside pangraph's presets)");
-	}
 
 	void ask_finish(QueryCtx &Q, RegTask &T, int rid, int32_t t_start, int32_t q_start, int q_rev)
 	{
@@ -704,11 +443,8 @@ struct Driver {
 						// whatever the answer, the second pass runs when both thresholds agree (they do in every asm preset): the return
 						// code is 1 or 2 (max_zdrop > zdrop_inv == zdrop), and 2 only sets split_inv of the piece split off here --
 						// so this region goes on with the second pass and leaves the query's answer to that piece
-						if (opt.zdrop == opt.zdrop_inv) { if (sg.job2 < 0) sg.job2 = second_pass(Q, T, sg, opt.zdrop); sg.zcode = 1; sg.ll_deferred = true; Q.jobs[(size_t)sg.ll_job].pad[1] = 1; }
-					} else {
-						int q_end, t_end;
-						sg.zcode = zcode_of(sg, ll_on_host(Q, 1 - T.rev, qlen - (sg.qs + sg.wq1), q_len, T.rid, sg.rs + sg.wt0, t_len, false, &q_end, &t_end));
-					}
+						if (opt.zdrop == opt.zdrop_inv) { if (sg.job2 < 0) sg.job2 = second_pass(Q, T, sg, opt.zdrop); sg.zcode = 1; sg.ll_deferred = true; }
+					} else ll_window_too_long(q_len, t_len);
 				}
 				if (sg.zcode > 0 && sg.job2 < 0) sg.job2 = second_pass(Q, T, sg, sg.zcode == 2 ? opt.zdrop_inv : opt.zdrop);
 				if (sg.ll_deferred && !have(Q, sg.job2)) return false;
@@ -781,15 +517,10 @@ struct Driver {
 			if (ql < opt.min_chain_score || ql > opt.max_gap) return 0;
 			if (tl < opt.min_chain_score || tl > opt.max_gap) return 0;
 			T.inv_ql = ql, T.inv_tl = tl;
-			if (ll_on_device(opt, ql, tl)) {
-				T.inv_ll_job = request(Q, q_strand, r1.rid, q_st, ql, r1.re, tl, 1, 0, -1, 0, PGA_JOB_LL);
-				T.inv_state = 3;
-				return 1;
-			}
-			int q_end, t_end;
-			const int score = ll_on_host(Q, q_strand, q_st, ql, r1.rid, r1.re, tl, true, &q_end, &t_end);
-			if (score < opt.min_dp_max) return 0;
-			extend_from(ql - (q_end + 1), tl - (t_end + 1));
+			if (!ll_on_device(opt, ql, tl)) ll_window_too_long(ql, tl);
+			T.inv_ll_job = request(Q, q_strand, r1.rid, q_st, ql, r1.re, tl, 1, 0, -1, 0, PGA_JOB_LL);
+			T.inv_state = 3;
+			return 1;
 		}
 		if (T.inv_state == 3) {
 			if (!have(Q, T.inv_ll_job)) return 1;
@@ -817,65 +548,6 @@ struct Driver {
 		return 0;
 	}
 };
-
-// parallel_for over a pool of persistent helper threads: a round of a small call runs a dozen of these loops, and starting eight
-// std::threads for each costs more than the loop (0.3 ms a time).  The caller always takes part, so a loop makes progress even when
-// every helper is busy with the loops of other batches; helpers join a loop through tickets and are counted, the caller leaves only when
-// the tickets nobody took are withdrawn and the helpers that joined are done.
-namespace {
-struct PfJob { std::atomic<size_t> next{0}; size_t n = 0, chunk = 1; void (*run)(void*, size_t) = nullptr; void *ctx = nullptr; int active = 0; std::exception_ptr err; };
-struct PfPool {
-	std::mutex mu; std::condition_variable cv_work, cv_done; std::deque<PfJob*> tickets; std::vector<std::thread> th; bool stop = false;
-	void loop(PfJob *j) { try { for (;;) { const size_t i0 = j->next.fetch_add(j->chunk); if (i0 >= j->n) break; const size_t i1 = std::min(j->n, i0 + j->chunk); for (size_t i = i0; i < i1; ++i) j->run(j->ctx, i); } } catch (...) { std::lock_guard<std::mutex> lk(mu); if (!j->err) j->err = std::current_exception(); j->next.store(j->n); } }
-	void worker() {
-		std::unique_lock<std::mutex> lk(mu);
-		for (;;) {
-			cv_work.wait(lk, [&] { return stop || !tickets.empty(); });
-			if (stop) return;
-			PfJob *j = tickets.front(); tickets.pop_front(); ++j->active;
-			lk.unlock(); loop(j); lk.lock();
-			if (--j->active == 0) cv_done.notify_all();
-		}
-	}
-	void grow(size_t want) { while (th.size() < want) th.emplace_back([this] { worker(); }); }     // (mu held)
-	~PfPool() { { std::lock_guard<std::mutex> lk(mu); stop = true; } cv_work.notify_all(); for (auto &t : th) t.join(); }
-};
-PfPool &pf_pool() { static PfPool *p = new PfPool(); return *p; }       // (leaked on purpose: no destructor order games at exit)
-}
-// what a call leaves behind on the host (thousands of small heap blocks near the root of a build) is freed by a janitor thread, off the call's path
-template <class T> static void scrap_later(std::vector<T> &&v)
-{
-	struct Janitor {
-		std::mutex mu; std::condition_variable cv; std::deque<std::vector<T>> q; std::thread th;
-		Janitor() : th([this] { for (;;) { std::vector<T> v; { std::unique_lock<std::mutex> lk(mu); cv.wait(lk, [&] { return !q.empty(); }); v = std::move(q.front()); q.pop_front(); } v.clear(); } }) { th.detach(); }
-	};
-	static Janitor *J = new Janitor();
-	{ std::lock_guard<std::mutex> lk(J->mu); J->q.push_back(std::move(v)); }
-	J->cv.notify_one();
-}
-// (the untyped form is what the other files of the library use: pga_common.h, pool_for)
-void pool_for_raw(size_t n, int n_threads, void (*run)(void*, size_t), void *ctx)
-{
-	if (n_threads <= 1 || n < 2) { for (size_t i = 0; i < n; ++i) run(ctx, i); return; }
-	// (items are taken a few at a time once there are thousands: one shared counter)
-	PfJob job; job.n = n; job.chunk = std::max<size_t>(1, n / 256); job.ctx = ctx; job.run = run;
-	const size_t helpers = std::min<size_t>((size_t)n_threads - 1, n - 1);
-	PfPool &P = pf_pool();
-	{
-		std::lock_guard<std::mutex> lk(P.mu);
-		P.grow(std::min<size_t>(64, std::max<size_t>(P.th.size(), (size_t)std::max(usable_cpus(), n_threads))));
-		for (size_t h = 0; h < helpers; ++h) P.tickets.push_back(&job);
-	}
-	P.cv_work.notify_all();
-	P.loop(&job);
-	{
-		std::unique_lock<std::mutex> lk(P.mu);
-		for (auto it = P.tickets.begin(); it != P.tickets.end();) it = *it == &job ? P.tickets.erase(it) : it + 1;
-		P.cv_done.wait(lk, [&] { return job.active == 0; });
-	}
-	if (job.err) std::rethrow_exception(job.err);
-}
-template <class F> static void parallel_for(size_t n, int n_threads, F f) { pool_for_raw(n, n_threads, [](void *c, size_t i) { (*static_cast<F*>(c))(i); }, &f); }
 
 // ---------------------------------------------------------------- device-side planning of a list of regions (pga_plan.hip)
 static void plan_list(const SeqSet &S, Driver &D, std::vector<std::pair<QueryCtx*, RegTask*>> &list, hipStream_t st, bool verbose)
@@ -918,51 +590,6 @@ struct RoundRunner {
 	const std::vector<int> &qs; int set_id, n_threads; hipStream_t st; Timers *tm; DpParams P;
 	bool verbose;
 	std::list<PinVec<uint32_t>> pools;        // CIGAR pools of the DP rounds: results point into them until the set is done
-	// Inversion queries nobody waits for (Seg::ll_deferred: the answer only sets split_inv of the piece split off there, which is read when that piece
-	// has been aligned, a round or more later): a 10 kb x 10 kb ksw_ll_i16 takes 13-21 ms, four times a round of end extensions.  They run BESIDE
-	// the rounds -- own host thread, stream, arena and launch lanes -- and are collected when they are done or when nothing else is left to do.
-	struct AsyncLL { std::thread th; std::atomic<bool> done{false}; std::vector<DpJob> jb; std::vector<std::pair<int,int>> owner; std::vector<DpRes> rs; PinVec<uint32_t> cg; Timers tm; std::string err; };
-	std::list<AsyncLL> asyncs;
-	void launch_async_ll(std::vector<DpJob> &&jb, std::vector<std::pair<int,int>> &&owner)
-	{
-		asyncs.emplace_back();
-		AsyncLL &A = asyncs.back();
-		A.jb = std::move(jb); A.owner = std::move(owner);
-		int dev = 0; PGA_HIP(hipGetDevice(&dev));
-		const PkBases bases = S.bases(); const DpParams Pc = P; const bool keep_tm = tm != nullptr;
-		A.th = std::thread([&A, dev, bases, Pc, keep_tm] {
-			hipStream_t ss = nullptr; int arena = -1;
-			try {
-				PGA_HIP(hipSetDevice(dev));
-				arena = dev_lease_arena();
-				ArenaScope arena_scope(arena);
-				set_thread_budget(1);
-				ss = stream_lease();
-				dp_run(bases, A.jb, Pc, A.rs, A.cg, ss, keep_tm ? &A.tm : nullptr);
-				PGA_HIP(sync_stream(ss));
-			} catch (std::exception &e) { A.err = e.what(); if (A.err.empty()) A.err = "unknown error"; }
-			if (ss) stream_release(ss);
-			if (arena >= 0) dev_release_arena(arena);
-			A.done.store(true, std::memory_order_release);
-		});
-	}
-	// results of the finished asynchronous queries into their queries' records (wait = true: of all of them); returns how many arrived
-	size_t harvest_async(bool wait)
-	{
-		size_t got = 0;
-		for (auto it = asyncs.begin(); it != asyncs.end();) {
-			AsyncLL &A = *it;
-			if (!wait && !A.done.load(std::memory_order_acquire)) { ++it; continue; }
-			A.th.join();
-			if (!A.err.empty()) { const std::string e = A.err; for (auto &B : asyncs) if (B.th.joinable()) B.th.join(); asyncs.clear(); throw std::runtime_error(e); }
-			for (size_t i = 0; i < A.rs.size(); ++i) { QueryCtx &q = Q[(size_t)A.owner[i].first]; const int id = A.owner[i].second; q.res[(size_t)id] = A.rs[i]; q.res[(size_t)id].pad = 1; q.cig[(size_t)id] = nullptr; }
-			if (tm) { tm->dp_bases += A.tm.dp_bases; for (int i = 0; i < K_COUNT; ++i) { tm->kern[i].ms += A.tm.kern[i].ms; tm->kern[i].launches += A.tm.kern[i].launches; tm->kern[i].alg_bytes += A.tm.kern[i].alg_bytes; tm->kern[i].cells += A.tm.kern[i].cells; } }
-			got += A.rs.size();
-			it = asyncs.erase(it);
-		}
-		return got;
-	}
-	~RoundRunner() { for (auto &A : asyncs) if (A.th.joinable()) A.th.join(); }
 
 	// identity probes: of the pending problems (answered ones leave the pending lists) and of the segments that have no problem record (Seg::job1 == -2:
 	// answered ones keep their count, the others become problems now)
@@ -970,7 +597,7 @@ struct RoundRunner {
 	{
 		const size_t n_q = qs.size();
 		std::vector<size_t> off(n_q + 1, 0);
-		parallel_for(n_q, n_threads, [&](size_t k) {
+		pool_for(n_q, n_threads, [&](size_t k) {
 			size_t c = 0; const QueryCtx &q = Q[(size_t)qs[k]];
 			for (int id : q.pending) c += q.jobs[(size_t)id].pad[0];
 			for (const RegTask *T : q.probe_tasks) for (const Seg &sg : T->segs) c += sg.job1 == -2 && sg.pm < 0;
@@ -980,7 +607,7 @@ struct RoundRunner {
 		const size_t n = off[n_q];
 		if (!n) return;
 		PinVec<PostProbe> pr; pr.resize(n);
-		parallel_for(n_q, n_threads, [&](size_t k) {
+		pool_for(n_q, n_threads, [&](size_t k) {
 			const QueryCtx &q = Q[(size_t)qs[k]]; size_t o = off[k];
 			for (int id : q.pending) { const DpJob &j = q.jobs[(size_t)id]; if (j.pad[0]) pr[o++] = PostProbe{j.t_off, j.q_off, j.qlen_full, j.qs, j.qlen, (int32_t)j.q_rev}; }
 			const uint64_t q_off = S.off[(size_t)q.qid];
@@ -993,7 +620,7 @@ struct RoundRunner {
 		const double t0 = wall_s();
 		post_identity(S.bases(), pr, D.probe_m_max, m, st);
 		std::atomic<size_t> n_yes(0);
-		parallel_for(n_q, n_threads, [&](size_t k) {
+		pool_for(n_q, n_threads, [&](size_t k) {
 			QueryCtx &q = Q[(size_t)qs[k]]; size_t o = off[k], w = 0, yes = 0;
 			for (size_t i = 0; i < q.pending.size(); ++i) {
 				const int id = q.pending[i];
@@ -1023,7 +650,7 @@ struct RoundRunner {
 		if (!n_pend) return;
 		std::vector<DpJob> jb(n_pend); std::vector<std::pair<int,int>> owner(n_pend);
 		std::vector<double> cells_of(n_q, 0.0);
-		parallel_for(n_q, n_threads, [&](size_t k) {
+		pool_for(n_q, n_threads, [&](size_t k) {
 			const size_t qi = (size_t)qs[k];
 			QueryCtx &q = Q[qi];
 			size_t o = poff[k]; double cells = 0;
@@ -1031,17 +658,6 @@ struct RoundRunner {
 			q.pending.clear();
 			cells_of[k] = cells;
 		});
-		static const bool async_ll = getenv("PGA_LL_ASYNC") != nullptr;     // measured: no gain (6.1-5.7 against 6.2-6.5 Gbp/s): one more stream and lane set per batch crowd the hardware queues
-		if (async_ll) {
-			std::vector<DpJob> ajb; std::vector<std::pair<int,int>> aown; size_t w = 0;
-			for (size_t i = 0; i < jb.size(); ++i) {
-				if ((jb[i].flag & PGA_JOB_LL) && jb[i].pad[1]) { ajb.push_back(jb[i]); aown.push_back(owner[i]); }
-				else { if (w != i) { jb[w] = jb[i]; owner[w] = owner[i]; } ++w; }
-			}
-			jb.resize(w); owner.resize(w);
-			if (!ajb.empty()) { if (verbose) fprintf(stderr, "[pga]   set %d round %d: %zu inversion queries run beside the rounds\n", set_id, round, ajb.size()); launch_async_ll(std::move(ajb), std::move(aown)); }
-			if (jb.empty()) return;
-		}
 		std::vector<DpRes> rs;
 		pools.emplace_back();
 		PinVec<uint32_t> &cg = pools.back();
@@ -1050,7 +666,7 @@ struct RoundRunner {
 		if (verbose) fprintf(stderr, "[pga]   set %d round %d: %zu DP problems in %.3f s\n", set_id, round, jb.size(), wall_s() - t_dp);
 		if (tm) { tm->dp_jobs += (double)jb.size(); for (double c : cells_of) tm->dp_cells += c; }
 		const uint32_t *base = cg.data();
-		parallel_for((rs.size() + 65535) / 65536, n_threads, [&](size_t blk) {
+		pool_for((rs.size() + 65535) / 65536, n_threads, [&](size_t blk) {
 			const size_t lo = blk * 65536, hi = std::min(rs.size(), lo + 65536);
 			for (size_t i = lo; i < hi; ++i) {
 				QueryCtx &q = Q[(size_t)owner[i].first]; const int id = owner[i].second;
@@ -1065,7 +681,7 @@ struct RoundRunner {
 	int advance_pass()
 	{
 		std::atomic<int> unfinished(0);
-		parallel_for(qs.size(), n_threads, [&](size_t k) {
+		pool_for(qs.size(), n_threads, [&](size_t k) {
 			const size_t qi = (size_t)qs[k];
 			QueryCtx &q = Q[qi];
 			if (q.finished) return;
@@ -1160,10 +776,10 @@ struct RoundRunner {
 		}
 		if (!fins.empty()) {
 			PinVec<uint32_t> ops; ops.resize(fin_ops);
-			parallel_for(ftask.size(), n_threads, [&](size_t i) { const auto &c = ftask[i]->r.cigar; if (!c.empty()) memcpy(ops.data() + fins[i].cig_off, c.data(), c.size() * 4); });
+			pool_for(ftask.size(), n_threads, [&](size_t i) { const auto &c = ftask[i]->r.cigar; if (!c.empty()) memcpy(ops.data() + fins[i].cig_off, c.data(), c.size() * 4); });
 			std::vector<PostFinRes> fr;
 			post_cigar_finish(S.bases(), fins, ops, P, fr, st);
-			parallel_for(ftask.size(), n_threads, [&](size_t i) {
+			pool_for(ftask.size(), n_threads, [&](size_t i) {
 				RegTask &T = *ftask[i]; Reg &r = T.r; const PostFinRes &f = fr[i];
 				r.cigar.assign(ops.data() + fins[i].cig_off, ops.data() + fins[i].cig_off + f.n_cigar);
 				if (f.qshift) { if (r.rev) r.qe -= f.qshift; else r.qs += f.qshift; }      // a leading insertion / deletion left the record (align.c:147-166)
@@ -1177,54 +793,8 @@ struct RoundRunner {
 		return true;
 	}
 
-	// Rounds are a barrier over the queries of the set: round r+1 starts when the slowest problem of round r is done.  After the bulk
-	// (round 0) only the few queries with split chains are left, each with its own CHAIN of dependent rounds (one per split point,
-	// second pass, inversion test) whose lengths and problem sizes have nothing to do with one another.  From then on every such
-	// query runs its rounds on its own (own host thread, stream, arena and launch lanes), a few at a time.
-	void run_tails(const std::vector<int> &open)
-	{
-		std::atomic<size_t> next(0);
-		std::vector<std::string> errs(open.size());
-		std::vector<Timers> tms(open.size());
-		std::vector<std::vector<int>> one(open.size());
-		int dev = 0; PGA_HIP(hipGetDevice(&dev));
-		auto worker = [&] {
-			for (;;) {
-				const size_t k = next.fetch_add(1);
-				if (k >= open.size()) break;
-				hipStream_t ss = nullptr;
-				const int arena = dev_lease_arena();
-				ArenaScope arena_scope(arena);
-				try {
-					PGA_HIP(hipSetDevice(dev));
-					set_thread_budget(1);
-					ss = stream_lease();
-					one[k].assign(1, open[k]);
-					Driver Dq(S, opt, D.k, ss); Dq.dev_plan = D.dev_plan; Dq.d_anchors = D.d_anchors;
-					RoundRunner R{S, opt, Dq, Q, out, one[k], set_id * 1000 + (int)k + 1, 1, ss, tm ? &tms[k] : nullptr, P, verbose, {}};
-					R.tail = true;
-					R.run();
-				} catch (std::exception &e) { errs[k] = e.what(); if (errs[k].empty()) errs[k] = "unknown error"; }
-				if (ss) stream_release(ss);
-				dev_release_arena(arena);
-			}
-		};
-		static const int conc = getenv("PGA_TAIL_THREADS") ? std::max(1, atoi(getenv("PGA_TAIL_THREADS"))) : 6;
-		std::vector<std::thread> th;
-		for (int t = 0; t < std::min<int>(conc, (int)open.size()); ++t) th.emplace_back(worker);
-		for (auto &t : th) t.join();
-		for (auto &e : errs) if (!e.empty()) throw std::runtime_error(e);
-		if (tm) for (const Timers &t : tms) {
-			tm->dp_jobs += t.dp_jobs; tm->dp_cells += t.dp_cells; tm->dp_bases += t.dp_bases; tm->dp_cigar_ops += t.dp_cigar_ops;
-			for (int i = 0; i < K_COUNT; ++i) { tm->kern[i].ms += t.kern[i].ms; tm->kern[i].launches += t.kern[i].launches; tm->kern[i].alg_bytes += t.kern[i].alg_bytes; tm->kern[i].cells += t.kern[i].cells; }
-		}
-	}
-
-	bool tail = false;
-
 	void run()
 	{
-		static const int tail_max = getenv("PGA_TAIL_QUERIES") ? atoi(getenv("PGA_TAIL_QUERIES")) : 0;      // off by default: measured slower (the extra streams and lane sets get in the way of the other parts), see DESIGN.md
 		for (int round = 0; round < 100000; ++round) {
 			const double t_r0 = wall_s();
 			run_probes();
@@ -1233,25 +803,11 @@ struct RoundRunner {
 			if (verbose) fprintf(stderr, "[pga]   set %d round %d: probes %.4f s, dp %.4f s\n", set_id, round, t_r1 - t_r0, wall_s() - t_r1);
 			const double t_adv0 = wall_s();
 			int unfinished;
-			harvest_async(false);
-			for (;;) {
-				for (;;) { unfinished = advance_pass(); bool more = run_plans(); more |= run_post(); if (!more) break; }
-				if (unfinished == 0) break;
-				bool pend = false; for (int qi : qs) pend |= !Q[(size_t)qi].pending.empty() || !Q[(size_t)qi].probe_tasks.empty();
-				if (pend || asyncs.empty()) break;
-				harvest_async(true);                               // nothing else to do: the queries that are still open wait for an inversion query
-			}
+			for (;;) { unfinished = advance_pass(); bool more = run_plans(); more |= run_post(); if (!more) break; }
 			if (verbose) fprintf(stderr, "[pga]   set %d round %d: host advance + device post-processing %.3f s\n", set_id, round, wall_s() - t_adv0);
-			if (unfinished == 0) { harvest_async(true); break; }       // (a query whose split left no piece never reads its answer: rare)
+			if (unfinished == 0) break;
 			bool any_pending = false; for (int qi : qs) any_pending |= !Q[(size_t)qi].pending.empty() || !Q[(size_t)qi].probe_tasks.empty();
 			if (!any_pending) throw std::runtime_error("pga: alignment driver stalled");
-			if (!tail && unfinished > 1 && unfinished <= tail_max) {
-				std::vector<int> open;
-				for (int qi : qs) if (!Q[(size_t)qi].finished) open.push_back(qi);
-				if (verbose) fprintf(stderr, "[pga]   set %d: %zu queries continue on their own after round %d\n", set_id, open.size(), round);
-				run_tails(open);
-				break;
-			}
 		}
 	}
 };
@@ -1284,7 +840,7 @@ void align_batch(const SeqSet &S, const mm_mapopt_t &opt, int k, const std::vect
 		head_off[(size_t)n_seq] = idx.size();
 		gather_anchors(idx, C.d_a.p, heads, st);
 	}
-	parallel_for((size_t)n_seq, n_threads, [&](size_t qi) {
+	pool_for((size_t)n_seq, n_threads, [&](size_t qi) {
 		QueryCtx &q = Q[qi];
 		q.qid = (int)qi, q.qlen = (int32_t)S.len[qi], q.rep_len = rep_len[qi]; q.base = (int)S.grp_off[S.grp_of_seq[qi]];
 		const int n_u = C.n_u[qi];
@@ -1362,10 +918,7 @@ void align_batch(const SeqSet &S, const mm_mapopt_t &opt, int k, const std::vect
 	scrap();
 	if (verbose) fprintf(stderr, "[pga]   align: contexts taken apart at +%.4f s\n", wall_s() - t_align0);
 	for (auto &e : errs) if (!e.empty()) throw std::runtime_error(e);
-	if (tm) for (const Timers &t : tms) {
-		tm->dp_jobs += t.dp_jobs; tm->dp_cells += t.dp_cells; tm->dp_bases += t.dp_bases; tm->dp_cigar_ops += t.dp_cigar_ops;
-		for (int i = 0; i < K_COUNT; ++i) { tm->kern[i].ms += t.kern[i].ms; tm->kern[i].launches += t.kern[i].launches; tm->kern[i].alg_bytes += t.kern[i].alg_bytes; tm->kern[i].cells += t.kern[i].cells; }
-	}
+	if (tm) for (const Timers &t : tms) *tm += t;
 }
 
 } // namespace pga

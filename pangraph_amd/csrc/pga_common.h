@@ -199,6 +199,14 @@ struct KernelStat { double ms = 0, launches = 0, alg_bytes = 0, cells = 0; };   
 struct Timers {
 	double upload = 0, sketch = 0, index = 0, seed = 0, chain = 0, align = 0, total = 0, dp_jobs = 0, dp_cells = 0, n_mz = 0, n_anchor = 0, dp_bases = 0, dp_cigar_ops = 0;
 	KernelStat kern[K_COUNT];   // device time of the path's own kernels, measured with HIP events on the launch stream
+	// what a concurrent worker (a query set) counted goes into its batch's record: every field that is accumulated.  (The stage wall times, `total`, n_mz
+	// and n_anchor are assigned once per batch by the pipeline, pga_api.cpp: they are not sums.)
+	Timers &operator+=(const Timers &t)
+	{
+		dp_jobs += t.dp_jobs; dp_cells += t.dp_cells; dp_bases += t.dp_bases; dp_cigar_ops += t.dp_cigar_ops;
+		for (int i = 0; i < K_COUNT; ++i) { kern[i].ms += t.kern[i].ms; kern[i].launches += t.kern[i].launches; kern[i].alg_bytes += t.kern[i].alg_bytes; kern[i].cells += t.kern[i].cells; }
+		return *this;
+	}
 };
 // Busy intervals (pga_busy_begin / pga_busy_end, pga_api.cpp): while a log is open, every event-bracketed launch of kernel family `kern`
 // leaves its interval [a, b] on the device's clock; the union per family and over all families is what a step really spent with that
@@ -230,10 +238,20 @@ void set_part_concurrency(int n);
 int part_concurrency();             // concurrent parts of this call, or batch calls in flight in the process, whichever is larger
 void batch_call_enter(); void batch_call_leave();
 struct SeqFrom { PkBases store; uint64_t pos; };       // where a sequence that is already resident lies (pga_batch_derive)
-// a loop over the library's pool of persistent helper threads (pga_align.cpp): the caller takes part, helpers join as they are free.  Starting std::threads
+// a loop over the library's pool of persistent helper threads (pga_pool.cpp): the caller takes part, helpers join as they are free.  Starting std::threads
 // per loop costs a stack mapping and its removal each (and the address-space lock of the whole process while six batches fault pages in).
 void pool_for_raw(size_t n, int n_threads, void (*run)(void*, size_t), void *ctx);
 template <class F> static inline void pool_for(size_t n, int n_threads, F f) { pool_for_raw(n, n_threads, [](void *c, size_t i) { (*static_cast<F*>(c))(i); }, &f); }
+// what a call leaves behind on the host (thousands of small heap blocks near the root of a build) is freed by a janitor thread (pga_pool.cpp), off the
+// call's path: one janitor per element type
+struct Janitor;
+Janitor *janitor_start();
+void janitor_take(Janitor *J, void *obj, void (*destroy)(void*));
+template <class T> inline void scrap_later(std::vector<T> &&v)
+{
+	static Janitor *J = janitor_start();
+	janitor_take(J, new std::vector<T>(std::move(v)), [](void *p) { delete static_cast<std::vector<T>*>(p); });
+}
 void upload_seqs(SeqSet &S, int n, const char *const *seq, const uint32_t *len, const char *const *name, int n_grp, const int64_t *grp_off, hipStream_t st,
                  const SeqFrom *from = nullptr, const uint8_t *const *from_probe = nullptr);
 void sketch_all(const SeqSet &S, int w, int k, Minimizers &M, hipStream_t st, Timers *tm = nullptr);

@@ -720,13 +720,7 @@ static void dp_run_impl(PkBases d_bases, const std::vector<DpJob> &jobs, const D
 	// launch order: the classes of few, long problems first -- their workgroups need most of a CU's LDS and would otherwise wait until the
 	// persistent waves of the million-problem classes (16 per CU, all of its LDS) have drained their queue
 	int lane_si[DP_NLANE] = {-1, -1, -1, -1, -1, -1, -1, -1, -1};
-	static const int launch_order_bulk[DP_NCLASS] = {13, 12, 9, 11, 7, 6, 5, 4, 3, 10, 2, 8, 1, 0};
-	// a round of the upper tree (a few hundred tiles, one or two banded fills): what it waits for are its longest single problems -- a thin tile of
-	// 10 k diagonals, an approximate fill on the lane kernel -- and every launch costs the host ~60 us: those go out first (a first-round call: the
-	// tile class ended 0.6-0.8 ms behind the others only because it was launched last)
-	static const int launch_order_small[DP_NCLASS] = {13, 10, 0, 1, 12, 9, 11, 7, 6, 5, 4, 3, 2, 8};
-	static const bool small_first = getenv("PGA_DP_SMALL_ORDER") != nullptr;     // (measured: the build is 5 % SLOWER with it -- off)
-	const int *launch_order = small_first && cls[0].size() + cls[1].size() <= 4096 ? launch_order_small : launch_order_bulk;
+	static const int launch_order[DP_NCLASS] = {13, 12, 9, 11, 7, 6, 5, 4, 3, 10, 2, 8, 1, 0};
 	for (int oi = 0; oi < DP_NCLASS; ++oi) {
 		const int c = launch_order[oi];
 		if (cls[c].empty()) continue;
@@ -752,11 +746,8 @@ static void dp_run_impl(PkBases d_bases, const std::vector<DpJob> &jobs, const D
 		X.n_waves = waves_of[c];
 		uint8_t *slab_p = lane_slab[lane_of_class[c]].p;
 		static const bool serial = getenv("PGA_DP_SERIAL") != nullptr;       // diagnosis: every class alone on the GPU, one after the other
-		static const bool on_main = getenv("PGA_DP_ON_MAIN") != nullptr;    // experiment: every class on the call's own stream (one hardware queue per batch)
-		static const bool three = getenv("PGA_DP_THREE_LANES") != nullptr;   // experiment: lane 3's classes (strips, class 3) share lane 1's stream
 		hipStream_t cs;
-		if (on_main) cs = st;
-		else if (dp_shared_streams()) {
+		if (dp_shared_streams()) {
 			// what the launch is expected to hold its queue for (ms): the long banded classes by their longest problem's nominal diagonals, the others by count
 			static const double base_ms[DP_NCLASS] = {1.5, 2.0, 4.0, 6.0, 10.0, 10.0, 10.0, 10.0, 0.5, 12.0, 5.0, 4.0, 2.0, 3.0};
 			double est = base_ms[c] * std::max(1.0, (double)ids.size() / (c <= 1 || c == 8 ? 20000.0 : c == 10 || c == 11 || c == 13 ? 512.0 : 64.0));
@@ -766,7 +757,7 @@ static void dp_run_impl(PkBases d_bases, const std::vector<DpJob> &jobs, const D
 			if (lsi < 0) lsi = dp_stream_pick(SP, est);
 			else { std::lock_guard<std::mutex> lk(SP.mu); SP.load[(size_t)lsi] += est; ++SP.pending[(size_t)lsi]; }
 			X.si = lsi; X.est = est; cs = SP.st[(size_t)X.si];
-		} else cs = lane_stream[serial ? 0 : (three && lane_of_class[c] == 3) ? 1 : lane_of_class[c]];
+		} else cs = lane_stream[serial ? 0 : lane_of_class[c]];
 		X.cs = cs;
 		// the problem list and the queue counter travel in the class's own lane stream: a copy queued in another stream can sit
 		// behind a long kernel that happens to share its hardware queue (streams outnumber the queues), and the host would wait for it

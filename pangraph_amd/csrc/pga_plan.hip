@@ -13,30 +13,16 @@
 //                       them -- a whole-genome chain of 250 000 anchors and 12 000 segments comes back as a few dozen records.
 //
 // The host (pga_align.cpp) used to download all anchors (0.5 GB per leaf batch), walk them four times per region and build a problem record per
-// segment; it now keeps control flow over the records this kernel returns.  Integer logic only; every loop below names the host function it
-// restates (pga_align.cpp) and the reference lines behind that.
+// segment; it now keeps control flow over the records this kernel returns.  Integer logic only.  The end trimming and the window arithmetic are the
+// functions of pga_plan.h that the host's Driver::plan calls too (it plans the regions this kernel hands back, and whole batches on the non-lean route);
+// every other loop below names the host function it restates (pga_align.cpp, pga_regions.cpp) and the reference lines behind that.
 #include "pga_common.h"
 #include "pga_plan.h"
 #include "pga_wave.h"
 
 namespace pga {
 
-static const uint64_t PA_LONG_JOIN = 1ULL << 40, PA_IGNORE = 1ULL << 41, PA_TANDEM = 1ULL << 42, PA_SELF = 1ULL << 43;
 #define PLAN_G_MAX 4096          // long gaps of one region kept in LDS; a region with more goes back to the host path
-
-struct DA {                       // device view of a query's compacted anchors (same accessors as pga_align.cpp: Anchors)
-	u128 *a; int32_t n;
-	__device__ __forceinline__ int32_t tpos(int i) const { return (int32_t)a[i].x; }
-	__device__ __forceinline__ int32_t qpos(int i) const { return (int32_t)a[i].y; }
-	__device__ __forceinline__ int32_t span(int i) const { return (int32_t)(a[i].y >> 32 & 0xff); }
-	__device__ __forceinline__ uint64_t target_key(int i) const { return a[i].x >> 32; }
-	__device__ __forceinline__ bool flagged(int i, uint64_t f) const { return (a[i].y & f) != 0; }
-	__device__ __forceinline__ int32_t indel(int i) const { return (qpos(i) - qpos(i - 1)) - (tpos(i) - tpos(i - 1)); }
-};
-
-__device__ __forceinline__ int plan_min(int a, int b) { return a < b ? a : b; }
-__device__ __forceinline__ int plan_max(int a, int b) { return a > b ? a : b; }
-__device__ __forceinline__ int plan_abs(int a) { return a < 0 ? -a : a; }
 
 // the n-th (0-based) set bit of m; m has more than n bits set
 __device__ __forceinline__ int nth_bit(unsigned long long m, int n) { for (int k = 0; k < n; ++k) m &= m - 1; return __ffsll((long long)m) - 1; }
@@ -51,7 +37,7 @@ void k_plan_regions(const PlanIn *__restrict__ in, uint32_t n_regions, u128 *__r
 	const uint32_t rid_x = blockIdx.x;
 	if (rid_x >= n_regions) return;
 	const PlanIn R = in[rid_x];
-	DA A{anchors + R.a_off, R.n_a};
+	Anchors A{anchors + R.a_off, R.n_a};
 	PlanOut O; memset(&O, 0, sizeof(O));
 	const int32_t qlen = R.qlen;
 	const int r_as = R.as, r_cnt = R.cnt;
@@ -60,7 +46,7 @@ void k_plan_regions(const PlanIn *__restrict__ in, uint32_t n_regions, u128 *__r
 	const uint64_t x0 = A.a[first].x;
 	const int32_t rid = (int32_t)(x0 << 1 >> 33), rev = (int32_t)(x0 >> 63);
 	const int32_t tlen_ref = (int32_t)seq_len[R.base + rid];
-	// ---- chain_extent (pga_align.cpp; hit.c:8-38) ----
+	// ---- chain_extent (pga_regions.cpp; hit.c:8-38) ----
 	int32_t r_rs, r_re, r_qs, r_qe, r_mlen, r_blen;
 	{
 		const int32_t sp0 = A.span(first);
@@ -94,30 +80,9 @@ void k_plan_regions(const PlanIn *__restrict__ in, uint32_t n_regions, u128 *__r
 		r_blen = (int32_t)((uint32_t)sp0 + (uint32_t)__builtin_amdgcn_readlane((int)wave_prefix_sum_incl(blk), 63));
 	}
 	O.rid = rid, O.rev = rev, O.r_rs = r_rs, O.r_re = r_re, O.r_qs = r_qs, O.r_qe = r_qe, O.r_mlen = r_mlen, O.r_blen = r_blen;
-	// ---- trim_chain_ends (align.c:471-509) ----
+	// ---- trim_chain_ends (pga_plan.h; align.c:471-509): uniform -- every lane walks the same few anchors, the loads are broadcast ----
 	int32_t as1 = r_as, cnt1 = r_cnt;
-	if (!P.no_end_flt && r_cnt >= 3) {
-		const int bw = P.bw, min_match = P.min_chain_score * 2;
-		// (uniform: every lane walks the same few anchors; the loads are broadcast)
-		int32_t len, match;
-		len = match = A.span(r_as);
-		for (int i = r_as + 1; i < last; ++i) {
-			if (A.flagged(i, PA_LONG_JOIN)) break;
-			const int32_t dt = A.tpos(i) - A.tpos(i - 1), dq = A.qpos(i) - A.qpos(i - 1), lo = plan_min(dt, dq), hi = plan_max(dt, dq);
-			if (hi - lo > len >> 1) as1 = i;
-			len += lo, match += plan_min(lo, A.span(i));
-			if (len >= bw << 1 || (match >= min_match && match >= bw) || match >= r_mlen >> 1) break;
-		}
-		cnt1 = last + 1 - as1;
-		len = match = A.span(last);
-		for (int i = last - 1; i > as1; --i) {
-			if (A.flagged(i + 1, PA_LONG_JOIN)) break;
-			const int32_t dt = A.tpos(i + 1) - A.tpos(i), dq = A.qpos(i + 1) - A.qpos(i), lo = plan_min(dt, dq), hi = plan_max(dt, dq);
-			if (hi - lo > len >> 1) cnt1 = i + 1 - as1;
-			len += lo, match += plan_min(lo, A.span(i + 1));
-			if (len >= bw << 1 || (match >= min_match && match >= bw) || match >= r_mlen >> 1) break;
-		}
-	}
+	if (!P.no_end_flt) trim_chain_ends(A, r_as, r_cnt, r_mlen, P.bw, P.min_chain_score * 2, as1, cnt1);
 	// ---- long gaps of [as1, as1 + cnt1): chain-relative indices with |indel| > 10, in order ----
 	int n_g = 0;
 	{
@@ -205,8 +170,8 @@ void k_plan_regions(const PlanIn *__restrict__ in, uint32_t n_regions, u128 *__r
 	__builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
 	for (int f = 0; f < n_f; ++f) {
 		const int from = s_F[2 * f], to = s_F[2 * f + 1];
-		if (to < 0) { if (lane == 0) A.a[as1 + from].y |= PA_LONG_JOIN; }
-		else for (int i = from + lane; i < to; i += 64) A.a[as1 + i].y |= PA_IGNORE;
+		if (to < 0) { if (lane == 0) A.a[as1 + from].y |= A_LONG_JOIN; }
+		else for (int i = from + lane; i < to; i += 64) A.a[as1 + i].y |= A_IGNORE;
 	}
 	__threadfence();
 	// ---- windows (align.c:633-696) ----
@@ -238,15 +203,6 @@ void k_plan_regions(const PlanIn *__restrict__ in, uint32_t n_regions, u128 *__r
 			if (n_same < 64) done = true;
 		}
 	}
-	if (qs > 0 && rs > 0) {
-		int32_t l = plan_min(qs, P.max_gap);
-		qs1 = plan_max(qs1, qs - l);
-		qs0 = plan_min(qs0, qs1);
-		l += l * P.a > P.q ? (l * P.a - P.q) / P.e : 0;
-		l = plan_min(plan_min(l, P.max_gap), rs);
-		rs1 = plan_max(rs1, rs - l);
-		rs0 = plan_min(plan_min(rs0, rs1), rs);
-	} else rs0 = rs, qs0 = qs;
 	re0 = A.tpos(r_as + r_cnt - 1) + 1, qe0 = A.qpos(r_as + r_cnt - 1) + 1;
 	re1 = tlen_ref, qe1 = qlen;
 	{
@@ -271,23 +227,7 @@ void k_plan_regions(const PlanIn *__restrict__ in, uint32_t n_regions, u128 *__r
 			if (n_same < 64) done = true;
 		}
 	}
-	if (qe < qlen && re < tlen_ref) {
-		int32_t l = plan_min(qlen - qe, P.max_gap);
-		qe1 = plan_min(qe1, qe + l);
-		qe0 = plan_max(qe0, qe1);
-		l += l * P.a > P.q ? (l * P.a - P.q) / P.e : 0;
-		l = plan_min(plan_min(l, P.max_gap), tlen_ref - re);
-		re1 = plan_min(re1, re + l);
-		re0 = plan_max(re0, re1);
-	} else re0 = re, qe0 = qe;
-	if (A.flagged(r_as, PA_SELF)) {
-		int max_ext = plan_abs(r_qs - r_rs);
-		if (r_rs - rs0 > max_ext) rs0 = r_rs - max_ext;
-		if (r_qs - qs0 > max_ext) qs0 = r_qs - max_ext;
-		max_ext = plan_abs(r_qe - r_re);
-		if (re0 - r_re > max_ext) re0 = r_re + max_ext;
-		if (qe0 - r_qe > max_ext) qe0 = r_qe + max_ext;
-	}
+	extension_windows(rs, qs, re, qe, rs0, qs0, re0, qe0, rs1, qs1, re1, qe1, qlen, tlen_ref, A.flagged(r_as, A_SELF), r_rs, r_qs, r_re, r_qe, P.max_gap, P.a, P.q, P.e);
 	O.as1 = as1, O.cnt1 = cnt1, O.rs = rs, O.qs = qs, O.rs0 = rs0, O.qs0 = qs0, O.re0 = re0, O.qe0 = qe0;
 	O.n_long_gaps = n_g; O.status = 0;
 	if (lane == 0) out[rid_x] = O;
@@ -325,8 +265,8 @@ void k_plan_cut(const PlanIn *__restrict__ in, uint32_t n_regions, const u128 *_
 		const u128 v = v_next;
 		if (i + 64 < cnt1) v_next = A[as1 + i + 64];                                   // (the next window is on its way while this one is cut: one wave, half a million anchors)
 		if (i < cnt1) {
-			const bool skip = (v.y & (PA_IGNORE | PA_TANDEM)) != 0 && i != cnt1 - 1;
-			use = !skip; lj = (v.y & PA_LONG_JOIN) != 0;
+			const bool skip = (v.y & (A_IGNORE | A_TANDEM)) != 0 && i != cnt1 - 1;
+			use = !skip; lj = (v.y & A_LONG_JOIN) != 0;
 			ce = (int32_t)v.x - half_k, cq = (int32_t)v.y - half_k;
 		}
 		const unsigned long long m_lj = __ballot(lj);
