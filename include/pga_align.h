@@ -127,6 +127,12 @@ int pga_stage_chain(const pga_params_t *params, int32_t n, const char *const *se
 int pga_stage_extd2(int32_t n_jobs, const uint8_t *const *q, const int32_t *qlen, const uint8_t *const *t, const int32_t *tlen,
                     int a, int b, int sc_ambi, int gapo, int gape, int gapo2, int gape2, const int32_t *w, const int32_t *zdrop, const int32_t *end_bonus, const int32_t *flag,
                     int32_t *ez, uint32_t **cigars, uint64_t *cigar_off);
+/* which kernel answered the DP problems of every call since the last one of this function (process-wide counters, copied out and zeroed):
+ * by_class[c] = problems launched in class c of dp_run (pga_ksw.hip: 0,1 register tiles, 2-4,7 workgroup kernel, 5 single wave, 6 ksw_ll_i16,
+ * 8 corridor, 9 strips, 10,11 lane kernels, 12 banded wave strips, 13 workgroup pipeline), second passes included; handed_back[0] = problems
+ * the workgroup pipeline gave to the other banded kernels, handed_back[1] = problems a corridor / banded / strip kernel gave to the full-matrix
+ * and workgroup kernels (no proof, a maximum outside 16 bits, a dry pool) */
+void pga_stage_dp_routes(int64_t by_class[14], int64_t handed_back[2]);
 /* radix_sort_128x (ksort.h:101-151, misc.c:155-159), the exact replay incl. the arrangement of equal keys: sorts every array
  * [seg_off[s], seg_off[s+1]) of the n_seg arrays in xy (two uint64 per record: x = key, y = payload) in place */
 int pga_stage_sort(int32_t n_seg, const uint64_t *seg_off, uint64_t *xy);

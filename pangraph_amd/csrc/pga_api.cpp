@@ -148,7 +148,9 @@ static void check_supported(const mm_mapopt_t &o, int k, int w)
 	if (!(o.flag & MM_F_NO_LJOIN)) throw std::runtime_error("pga: long-join re-chaining is not implemented (pangraph always passes -X)");
 	if (!(o.flag & MM_F_ALL_CHAINS)) throw std::runtime_error("pga: primary/secondary selection is not implemented (pangraph always passes -X)");
 	if (o.q == o.q2 && o.e == o.e2) throw std::runtime_error("pga: single-affine scoring (ksw_extz2) is out of scope");
-	if (-(-o.b) > 2 * (o.q + o.e) && o.b > 2 * (o.q + o.e)) throw std::runtime_error("pga: mismatch penalty larger than 2*(q+e) disables the reference DP");
+	// (the reference tests behind its exchange of the two pairs, ksw2_extd2_sse.c:78 and :100: against the cheaper one, and returns an empty record for every problem)
+	const int qe_min = std::min(o.q + o.e, o.q2 + o.e2);
+	if (o.b > 2 * qe_min) throw std::runtime_error("pga: mismatch penalty b = " + std::to_string(o.b) + " is larger than 2*(q+e) = " + std::to_string(2 * qe_min) + " of the cheaper gap pair: that disables the reference DP");
 	if (k > 28 || k < 1 || w < 1 || w > 255) throw std::runtime_error("pga: k must be in [1,28] and w in [1,255]");
 	if (o.sdust_thres > 0) throw std::runtime_error("pga: SDUST masking is not implemented");
 	// the inversion test (ksw_ll_i16, align.c:845-855) runs over windows of up to max_gap bases and the device kernel holds 10 240: refused
@@ -811,6 +813,8 @@ extern "C" int pga_stage_extd2(int32_t n_jobs, const uint8_t *const *q, const in
 		return 0;
 	} catch (std::exception &e) { set_err(e.what()); return -1; }
 }
+
+extern "C" void pga_stage_dp_routes(int64_t by_class[14], int64_t handed_back[2]) { dp_routes_take(by_class, handed_back); }
 
 // ---------------------------------------------------------------- split_matches + filter_matches on the device (pga_filter.hip)
 namespace pga {

@@ -75,6 +75,7 @@ __host__ __device__ inline bool lb_final(const LbStop &S, int r, int tlen, int q
 }
 
 int dp_lb_mode();          // PGA_LB=off: 1, PGA_LB=check: 2 (read on every call: tests switch it inside one process), else 0
+void dp_routes_take(int64_t by_class[14], int64_t handed_back[2]);   // the route counters since the last call, zeroed (pga_stage_dp_routes)
 size_t dp_slab_bytes(int qlen, int tlen, int w);
 void dp_run(PkBases d_bases, const std::vector<DpJob> &jobs, const DpParams &P, std::vector<DpRes> &res, PinVec<uint32_t> &cigars, hipStream_t st, Timers *tm = nullptr);
 

@@ -445,6 +445,15 @@ size_t dp_trim_lane_sets()
 	return bytes;
 }
 
+// Route counters of the stage tap pga_stage_dp_routes (tests): problems per class as launched, problems handed back per pass of dp_run.  Process-wide,
+// one atomic add per class and call.
+static std::atomic<int64_t> g_route_class[DP_NCLASS], g_route_back[2];
+void dp_routes_take(int64_t by_class[DP_NCLASS], int64_t handed_back[2])
+{
+	for (int c = 0; c < DP_NCLASS; ++c) by_class[c] = g_route_class[c].exchange(0);
+	for (int p = 0; p < 2; ++p) handed_back[p] = g_route_back[p].exchange(0);
+}
+
 int dp_lb_mode() { const char *e = getenv("PGA_LB"); return !e ? 0 : !strcmp(e, "off") || !strcmp(e, "0") ? 1 : !strcmp(e, "check") ? 2 : 0; }
 
 void dp_run(PkBases d_bases, const std::vector<DpJob> &jobs, const DpParams &P, std::vector<DpRes> &res, PinVec<uint32_t> &cigars, hipStream_t st, Timers *tm)
@@ -460,6 +469,7 @@ void dp_run(PkBases d_bases, const std::vector<DpJob> &jobs, const DpParams &P, 
 			if (res[i].n_cigar == (pass == 1 ? -10 : -9)) redo.push_back((uint32_t)i);
 		}
 		if (redo.empty()) continue;
+		g_route_back[pass - 1] += (int64_t)redo.size();
 		if (getenv("PGA_VERBOSE")) fprintf(stderr, "[pga]     %s: %zu of %zu problems handed back\n", pass == 1 ? "workgroup pipeline -> lane kernels / wave strips" : "corridor / banded kernels -> workgroup kernel", redo.size(), jobs.size());
 		std::vector<DpJob> jb(redo.size());
 		for (size_t k = 0; k < redo.size(); ++k) jb[k] = jobs[redo[k]];
@@ -612,6 +622,7 @@ static void dp_run_impl(PkBases d_bases, const std::vector<DpJob> &jobs, const D
 			for (uint32_t id : take) { cls_of[id] = 12; need[id] = bstrips_slab_bytes(jobs[id]); slab_max[12] = std::max(slab_max[12], need[id]); }
 		}
 	}
+	for (int c = 0; c < DP_NCLASS; ++c) if (!cls[c].empty()) g_route_class[c] += (int64_t)cls[c].size();      // (behind the re-bucketing: what is launched)
 	res.resize(n);
 	DBuf<uint32_t> d_pool((size_t)cig_total + 1);
 	// the CIGAR pool's cursor and every class's queue counters in one block, zeroed once (a memset dispatch per class before)

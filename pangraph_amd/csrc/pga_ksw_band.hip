@@ -43,8 +43,11 @@ void k_gapfill_band(const DpJob *__restrict__ jobs, uint32_t n_jobs, PkBases bas
 	__shared__ uint32_t s_cig[2][BAND_MAXCIG + 8];
 	const int lane = threadIdx.x, g = lane >> 5, gl = lane & 31;
 	uint8_t *slab = slab_all + (size_t)blockIdx.x * slab_bytes + (size_t)g * (slab_bytes / 2);
-	const int q = P.q, e = P.e, q2 = P.q2, e2 = P.e2;
-	const int sc_mch = P.sc_mch, sc_mis = P.sc_mis, sc_N = P.sc_ambi == 0 ? -e2 : P.sc_ambi;
+	// (q, e) is the pair that is cheaper to open, as in the other classes: the gap states 1/2 and 3/4 of the direction byte, their tie order and the score of
+	// an N under sc_ambi = 0 (-e2) are the reference's only after its exchange (ksw2_extd2_sse.c:78, :87)
+	const GapCosts G(P);
+	const int q = G.q, e = G.e, q2 = G.q2, e2 = G.e2;
+	const int sc_mch = P.sc_mch, sc_mis = P.sc_mis, sc_N = G.sc_N;
 
 	for (;;) {
 		uint32_t j0 = 0;
@@ -207,7 +210,9 @@ void k_gapfill_band(const DpJob *__restrict__ jobs, uint32_t n_jobs, PkBases bas
 		if (gl == 0 && on) {
 			DpRes R;
 			R.max = 0, R.max_q = -1, R.max_t = -1, R.mqe = KSW_NEG_INF, R.mqe_t = -1, R.mte = KSW_NEG_INF, R.mte_q = -1;
-			R.score = ok ? score : KSW_NEG_INF; R.zdropped = 0, R.reach_end = 0;
+			// (the reference's H(0,0) is v - qe with qe taken BEFORE the exchange, ksw2_extd2_sse.c:68 and :379: under exchanged pairs every H, and the
+			// score it reports, lies q + e - (q2 + e2) below the alignment's; the corridor's scores are absolute)
+			R.score = ok ? score - (G.qe_h - G.qe) : KSW_NEG_INF; R.zdropped = 0, R.reach_end = 0;
 			R.n_cigar = ok ? n_cigar : -9;                       // -9: not proven inside the corridor, run the full matrix
 			R.pad = 0, R.cigar_off = base;
 			res[jid] = R;

@@ -224,7 +224,7 @@ __device__ __forceinline__ void wstrip_body(const DpJob &J, const uint32_t jl, c
 	// score of the path: cig_tmp runs from the end of the alignment to its start
 	int score = KSW_NEG_INF;
 	if (n_cigar > 0 && !zdropped) {
-		int ti = tlen, qj = qlen; score = 0;
+		int ti = tlen, qj = qlen; score = qe - qe_h;          // (every H of the reference carries its first cell's v - qe, qe taken before the exchange of the pairs: ksw2_extd2_sse.c:68, :358, :379)
 		for (int c = 0; c < n_cigar; ++c) {
 			const uint32_t op = cig_tmp[c] & 0xf; const int len = (int)(cig_tmp[c] >> 4);
 			if (op == 0) {

@@ -183,6 +183,14 @@ def product_extd2(dll, jobs, a, b, sc_ambi, gapo, gape, gapo2, gape2):
     return out
 
 
+def product_dp_routes(dll):
+    """pga_stage_dp_routes: (by_class[14], handed_back[2]) of every DP call since the last read; the read zeroes the counters"""
+    by_class, handed_back = (C.c_int64 * 14)(), (C.c_int64 * 2)()
+    dll.pga_stage_dp_routes.restype = None
+    dll.pga_stage_dp_routes(by_class, handed_back)
+    return list(by_class), list(handed_back)
+
+
 # ---------------------------------------------------------------- anchors + chains
 def oracle_anchors(dll, seqs, names, opt: mm_mapopt_t, w, k):
     """per query: sorted anchor list [(x,y)], rep_len -- oracle restatement of map.c:168-204"""
