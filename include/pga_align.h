@@ -183,7 +183,8 @@ int pga_stage_mash_sketch(int32_t n, const char *const *seqs, const uint32_t *le
  * its boundary (align/nextclade/align/align.rs:55-62), then insertions_strip / find_nuc_changes and the terminal deletions.
  * One job per member sequence; ref and qry are upper-case IUPAC letters (not NUL-terminated); jobs that share a consensus should
  * pass the same pointer (it is uploaded once).  The caller keeps Edit::apply, reverse_complement and BandParameters::from_edits
- * (reweave.rs:53-75).  Per job: status 0, or the reference's error -- 1 the query is shorter than min_length (align.rs:42-46),
+ * (reweave.rs:53-75): the entry for hosts that already hold member sequences.  A host that holds a block as pangraph does, a consensus and
+ * one edit list per member, calls pga_solve_promises below, which does those three on the way.  Per job: status 0, or the reference's error -- 1 the query is shorter than min_length (align.rs:42-46),
  * 2 a letter to_nuc rejects (alphabet/nuc.rs:99-121) or a literal '-' in ref / qry (to_nuc accepts it, the edit extraction of the reference would
  * read it as an alignment gap; block sequences never contain one, so it is rejected instead of reproduced), 3 the traceback left the band (the reference panics).  Substitutions in
  * reference order, deletions as the reference pushes them (internal ones ascending, then the leading, then the trailing one),
@@ -239,6 +240,50 @@ typedef struct {
 int pga_reconsensus(int64_t n_blocks, const pga_rc_block_t *blocks, const pga_rc_member_t *members, const pga_sub_t *subs, const pga_del_t *dels,
                     const pga_ins_t *inss, const char *ins_seq, const pga_mapvar_params_t *params, pga_rc_out_t *out);
 void pga_rc_free(pga_rc_out_t *out);
+
+/* ---- SURVEY 8(f)-1, the whole step: MergePromise::solve_promise (packages/pangraph/src/pangraph/reweave.rs:40-94) for all promises of a merge ----
+ * pga_solve_promises takes what a pangraph host holds -- per promise the two consensus sequences, the orientation and the CIGAR of the
+ * match, per member of the append block its edits against the append consensus -- and returns every member's edits against the ANCHOR
+ * consensus.  Member sequences are built on the device and feed the aligner there; what is handed over is the consensus sequences and the
+ * edit lists.  Input layout as for pga_reconsensus: the members of promise p are the next promises[p].n_members entries of members[] (the
+ * reference's BTreeMap order), a member's edits the next n_subs / n_dels / n_inss entries of subs / dels / inss.  Output layout as for
+ * pga_map_variations: res[m] (one per member, input order) holds offsets into the four arrays, which are freed with pga_free(); the
+ * arrays are packed member by member in input order.  Promises onto the same consensus should pass the same pointer (uploaded once).
+ * Per member, in the reference's order (reweave.rs:46-81):
+ *   1. the cigar band: BandParameters::from_edits(Edit::from_cigar(cigar), anchor_len) (edits.rs:538-566; M = X advance, I an insertion at
+ *      the current position, D a deletion), once per promise.  No aligned position: status 8 for EVERY member of the promise, the empty
+ *      ones included (the reference fails before its loop).
+ *   2. seq = edits.apply(append consensus) (edits.rs:307-329, list-order rules as in pga_reconsensus).  An empty seq: status 0 and the
+ *      single deletion (0, anchor_len); no alignment, no band, orientation ignored.
+ *   3. reverse != 0: seq is reverse-complemented with the table of io/seq.rs:9-29 (ACGTYRWSKMDVHBN- and nothing else; lower case is
+ *      rejected) and the band of step 4 is that of edits.reverse_complement(append_len) (edits.rs:257-276: sub len-pos-1, del
+ *      len-pos-len, ins len-pos, each list stably sorted by position).  A rejected letter in the sequence or in an edit: status 9.
+ *   4. the member band: BandParameters::from_edits(edits as oriented, append_len); no aligned position: status 7 (as pga_reconsensus).
+ *      mean_shift and band_width are the sums of the cigar's and the member's (map_variations.rs:23-26).
+ *   5. map_variations(anchor consensus, seq, band): status 1, 2, 3 as pga_map_variations; extra_band_width is added inside, as there.
+ * A literal '-' in a consensus or in an insertion is handled as pga_reconsensus handles it: it is NOT stripped by the apply step (the
+ * reference's Edit::apply would drop it with the gaps of its deletions, edits.rs:326), it stays in the sequence, and the alignment rejects
+ * the member with status 2 (forward or reverse: '-' complements to itself).  Block sequences never contain one.
+ * Malformed input fails the call (-1; the reference panics or hits unimplemented!): a CIGAR operation other than M I D = X, an edit
+ * position or interval outside the append consensus, a NULL sequence with a non-zero length.
+ * PGA_PROMISE_CHUNK_MB (default 2048) caps the built sequences held on the device at once; promises are processed in chunks under it
+ * (a single promise is never split) and the result does not depend on it.  Returns 0, or -1 with the message in pga_last_error(). */
+typedef struct {
+	const char *anchor; uint32_t anchor_len;     /* anchor_block.consensus() */
+	const char *append; uint32_t append_len;     /* append_block.consensus() */
+	int32_t reverse;                             /* !orientation.is_forward() */
+	const uint32_t *cigar; uint32_t n_cigar;     /* minimap2 packing: len << 4 | op, op in M(0) I(1) D(2) =(7) X(8) */
+	uint32_t n_members;                          /* append_block.alignments(), BTreeMap order */
+} pga_promise_t;
+int pga_solve_promises(int64_t n_promises, const pga_promise_t *promises, const pga_rc_member_t *members, const pga_sub_t *subs, const pga_del_t *dels,
+                       const pga_ins_t *inss, const char *ins_seq, const pga_mapvar_params_t *params, pga_mapvar_res_t *res,
+                       pga_sub_t **out_subs, pga_del_t **out_dels, pga_ins_t **out_inss, char **out_ins_seq);
+/* stage tap: steps 1-4 alone.  Per member (input order) the status reached before alignment (0, 7, 8 or 9; 0 with an empty sequence
+ * for the member of step 2), the summed band before extra_band_width (0, 0 where the status is not 0 or the sequence is empty) and the
+ * oriented sequence as the aligner would read it: seqs[seq_off[m] .. seq_off[m + 1]), empty where the status is not 0.  seq_off has one
+ * more entry than there are members; *seqs is freed with pga_free(). */
+int pga_stage_promise_jobs(int64_t n_promises, const pga_promise_t *promises, const pga_rc_member_t *members, const pga_sub_t *subs, const pga_del_t *dels,
+                           const pga_ins_t *inss, const char *ins_seq, int32_t *status, int32_t *mean_shift, uint32_t *band_width, uint64_t *seq_off, char **seqs);
 int pga_stats_version(void);     /* == PGA_STATS_VERSION of the header the library was built with */
 /* Measurement only (no reference interface behind it): the kern_ms sums of pga_stats_t count overlapping launches on different streams
  * and batches several times.  Between pga_busy_begin() and pga_busy_end() every event-bracketed launch of the process leaves its interval

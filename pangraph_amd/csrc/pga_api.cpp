@@ -928,6 +928,48 @@ extern "C" int pga_reconsensus(int64_t n_blocks, const pga_rc_block_t *blocks, c
 	catch (std::exception &e) { pga_rc_free(out); set_err(e.what()); return -1; }
 }
 
+// ---------------------------------------------------------------- SURVEY 8(f)-1, the whole step: solve_promise (pga_promise.hip)
+namespace pga {
+struct PromiseStage { int32_t *status, *mean_shift; uint32_t *band_width; uint64_t *seq_off; std::vector<char> seqs; };
+void solve_promises_host(int64_t n_promises, const pga_promise_t *promises, const pga_rc_member_t *members, const pga_sub_t *subs, const pga_del_t *dels, const pga_ins_t *inss,
+                         const char *ins_seq, const pga_mapvar_params_t &prm, pga_mapvar_res_t *res, std::vector<pga_sub_t> &o_subs, std::vector<pga_del_t> &o_dels,
+                         std::vector<pga_ins_t> &o_inss, std::vector<char> &o_iseq, PromiseStage *stage);
+}
+extern "C" int pga_solve_promises(int64_t n_promises, const pga_promise_t *promises, const pga_rc_member_t *members, const pga_sub_t *subs, const pga_del_t *dels,
+                                  const pga_ins_t *inss, const char *ins_seq, const pga_mapvar_params_t *params, pga_mapvar_res_t *res,
+                                  pga_sub_t **out_subs, pga_del_t **out_dels, pga_ins_t **out_inss, char **out_ins_seq)
+{
+	try {
+		require_device();
+		if (n_promises < 0 || (n_promises && !promises) || !params || !out_subs || !out_dels || !out_inss || !out_ins_seq) throw std::runtime_error("pga_solve_promises: null argument");
+		int64_t n_mem = 0;
+		for (int64_t p = 0; p < n_promises; ++p) n_mem += promises[p].n_members;
+		if (n_mem && !res) throw std::runtime_error("pga_solve_promises: null argument");
+		std::vector<pga_sub_t> s; std::vector<pga_del_t> d; std::vector<pga_ins_t> i; std::vector<char> q;
+		if (n_promises) pga::solve_promises_host(n_promises, promises, members, subs, dels, inss, ins_seq, *params, res, s, d, i, q, nullptr);
+		*out_subs = dup_out(s); *out_dels = dup_out(d); *out_inss = dup_out(i); *out_ins_seq = dup_out(q);
+		return 0;
+	} catch (std::exception &e) { set_err(e.what()); return -1; }
+}
+extern "C" int pga_stage_promise_jobs(int64_t n_promises, const pga_promise_t *promises, const pga_rc_member_t *members, const pga_sub_t *subs, const pga_del_t *dels,
+                                      const pga_ins_t *inss, const char *ins_seq, int32_t *status, int32_t *mean_shift, uint32_t *band_width, uint64_t *seq_off, char **seqs)
+{
+	try {
+		require_device();
+		if (n_promises < 0 || (n_promises && !promises) || !seq_off || !seqs) throw std::runtime_error("pga_stage_promise_jobs: null argument");
+		int64_t n_mem = 0;
+		for (int64_t p = 0; p < n_promises; ++p) n_mem += promises[p].n_members;
+		if (n_mem && (!status || !mean_shift || !band_width)) throw std::runtime_error("pga_stage_promise_jobs: null argument");
+		pga::PromiseStage S{status, mean_shift, band_width, seq_off, {}};
+		seq_off[0] = 0;
+		std::vector<pga_sub_t> s; std::vector<pga_del_t> d; std::vector<pga_ins_t> i; std::vector<char> q;
+		pga_mapvar_params_t none; memset(&none, 0, sizeof(none));
+		if (n_promises) pga::solve_promises_host(n_promises, promises, members, subs, dels, inss, ins_seq, none, nullptr, s, d, i, q, &S);
+		*seqs = dup_out(S.seqs);
+		return 0;
+	} catch (std::exception &e) { set_err(e.what()); return -1; }
+}
+
 extern "C" int pga_stage_sort(int32_t n_seg, const uint64_t *seg_off, uint64_t *xy)
 {
 	try {
