@@ -284,6 +284,62 @@ int pga_solve_promises(int64_t n_promises, const pga_promise_t *promises, const 
  * more entry than there are members; *seqs is freed with pga_free(). */
 int pga_stage_promise_jobs(int64_t n_promises, const pga_promise_t *promises, const pga_rc_member_t *members, const pga_sub_t *subs, const pga_del_t *dels,
                            const pga_ins_t *inss, const char *ins_seq, int32_t *status, int32_t *mean_shift, uint32_t *band_width, uint64_t *seq_off, char **seqs);
+
+/* ---- between the two: block_slice (packages/pangraph/src/pangraph/slice.rs:12-202) for every interval a merge cuts its blocks into ----
+ * pga_slice_blocks replaces the loop of reweave.rs:427-438 over split_block (reweave.rs:342-402): for every block that takes part in a
+ * merge and every interval of it, every member's edits are filtered, clipped and shifted (slice.rs:12-53), its coordinates inside the
+ * interval computed (interval_node_coords, slice.rs:103-127), from those the new node's position on its path and its strand
+ * (new_position_circular / _non_circular, new_strandedness, slice.rs:55-101), and the member left out of the slice when its alignment has
+ * become empty (Edit::is_empty_alignment, edits.rs:351-367).  The aligned slices are the append_block / anchor_block of the
+ * MergePromises: pga_result_filter -> pga_slice_blocks -> pga_solve_promises is a merge in one data layout.  extract_intervals, the block
+ * and node ids, group_promises / update_cigar and graph.update stay with the caller.
+ * Input layout as for pga_reconsensus: the members of block b are the next blocks[b].n_members entries of members[] and of nodes[], its
+ * intervals the next blocks[b].n_intervals entries of intervals[], a member's edits the next n_subs / n_dels / n_inss entries of subs /
+ * dels / inss.  Insertion letters are not read (only pga_ins_t.len) and not copied: a sliced insertion keeps its seq_off into the
+ * caller's ins_seq.  Consensus letters are not read either: the consensus of a slice is consensus + start, end - start letters.
+ * Output (freed with pga_slice_free): slices[] ordered by (block, interval); the kept members of a slice are members[member_off ..
+ * member_off + n_kept) in input member order, their edits packed in that order, so that counts + member_off and subs + sub_off /
+ * dels + del_off / inss + ins_off of the slice's first kept member are what pga_solve_promises and pga_reconsensus take (pointer
+ * arithmetic only; the caller's ins_seq goes with them unchanged); dropped[] holds, slice after slice (n_dropped each, starting at the sum of the n_dropped
+ * before), the member indices whose slice is empty -- the None entries of node_updates (slice.rs:187-190).
+ *   substitutions  kept iff start <= pos < end; pos -= start; list order kept
+ *   deletions      kept iff end > pos && start < pos + len, clipped to the interval and shifted (a zero-length one strictly inside an
+ *                  interval is kept, one at pos == start is not; a deletion appears in every interval it overlaps)
+ *   insertions     kept iff start <= pos < end, or pos == cons_len == end; pos -= start
+ *   coordinates    slice.rs:103-127 as written: node_start = start - D(start) + I(start), node_end = end - D(end) + I(end) plus the
+ *                  insertions at cons_len when end == cons_len; D(x) = the deleted positions below x, a position that two deletions share
+ *                  counted twice as there, I(x) = the letters inserted before x
+ *   position       64-bit; circular paths modulo path_len (a node over its whole path comes out as (0, 0))
+ *   emptiness      no inserted letter, deletion lengths >= end - start, and the union of the deletions covers the slice (what
+ *                  apply(...).len() == 0 says; lengths that add up over a gap are not empty).  A literal '-' in a consensus or a
+ *                  substitution to '-' is treated as the other entries treat it: NOT stripped (the reference's Edit::apply would drop it
+ *                  with the gaps of its deletions); block sequences never contain one.
+ * The intervals of a block are sorted by start, non-empty, disjoint and inside [0, cons_len]; the reference's tile the block
+ * (pangraph_interval.rs:57-96), gaps between them are allowed here and receive nothing.  Malformed input fails the call (-1, message in
+ * pga_last_error(); the reference panics or trips sanity_check): intervals that break that rule, an edit position or deletion end
+ * beyond cons_len, cons_len == 0, a NULL list with a non-zero count, a circular node with path_len == 0, a reverse node whose pos_end
+ * (plus path_len on a circular path) is smaller than its node_end, overlapping deletions that remove more positions than lie before an
+ * interval boundary (usize underflow in slice.rs:108/112), more than 2^32 edits of one kind in one block. */
+typedef struct { const char *consensus; uint32_t cons_len, n_members, n_intervals; } pga_slice_block_t;
+typedef struct { uint32_t start, end; int32_t flip; } pga_slice_interval_t;   /* flip = aligned && !is_anchor && the orientation is reverse: new_strandedness reverses the strand */
+typedef struct { uint64_t pos_start, pos_end, path_len; int32_t reverse, circular; } pga_slice_node_t;   /* the OLD node of a member: position(), its path's tot_len, strand, circular() */
+typedef struct {
+	uint32_t member;                  /* index of the member inside its block (input order) */
+	int32_t  reverse;                 /* new strand */
+	uint32_t node_start, node_end;    /* interval_node_coords */
+	uint64_t pos_start, pos_end;      /* new position on the path */
+	pga_rc_member_t counts;           /* n_subs, n_dels, n_inss of the sliced edit */
+	uint64_t sub_off, del_off, ins_off;   /* its first entry in out->subs / dels / inss */
+} pga_slice_member_t;
+typedef struct { uint64_t member_off; uint32_t n_kept, n_dropped; } pga_slice_res_t;   /* one per (block, interval) */
+typedef struct {
+	pga_slice_res_t *slices; pga_slice_member_t *members;
+	pga_rc_member_t *counts;          /* counts[k] == members[k].counts, packed: the members[] argument of pga_solve_promises / pga_reconsensus */
+	uint32_t *dropped; pga_sub_t *subs; pga_del_t *dels; pga_ins_t *inss;
+} pga_slice_out_t;
+int pga_slice_blocks(int64_t n_blocks, const pga_slice_block_t *blocks, const pga_slice_interval_t *intervals, const pga_rc_member_t *members, const pga_slice_node_t *nodes,
+                     const pga_sub_t *subs, const pga_del_t *dels, const pga_ins_t *inss, pga_slice_out_t *out);
+void pga_slice_free(pga_slice_out_t *out);
 int pga_stats_version(void);     /* == PGA_STATS_VERSION of the header the library was built with */
 /* Measurement only (no reference interface behind it): the kern_ms sums of pga_stats_t count overlapping launches on different streams
  * and batches several times.  Between pga_busy_begin() and pga_busy_end() every event-bracketed launch of the process leaves its interval

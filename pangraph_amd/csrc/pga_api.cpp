@@ -970,6 +970,30 @@ extern "C" int pga_stage_promise_jobs(int64_t n_promises, const pga_promise_t *p
 	} catch (std::exception &e) { set_err(e.what()); return -1; }
 }
 
+// ---------------------------------------------------------------- block_slice for a merge's intervals (pga_slice.hip)
+namespace pga {
+void slice_blocks_host(int64_t n_blocks, const pga_slice_block_t *blocks, const pga_slice_interval_t *intervals, const pga_rc_member_t *members, const pga_slice_node_t *nodes,
+                       const pga_sub_t *subs, const pga_del_t *dels, const pga_ins_t *inss, pga_slice_out_t *out);
+}
+extern "C" void pga_slice_free(pga_slice_out_t *o)
+{
+	if (!o) return;
+	free(o->slices); free(o->members); free(o->counts); free(o->dropped); free(o->subs); free(o->dels); free(o->inss);
+	memset(o, 0, sizeof(*o));
+}
+extern "C" int pga_slice_blocks(int64_t n_blocks, const pga_slice_block_t *blocks, const pga_slice_interval_t *intervals, const pga_rc_member_t *members, const pga_slice_node_t *nodes,
+                                const pga_sub_t *subs, const pga_del_t *dels, const pga_ins_t *inss, pga_slice_out_t *out)
+{
+	if (!out) { set_err("pga_slice_blocks: null output"); return -1; }
+	memset(out, 0, sizeof(*out));
+	try {
+		require_device();
+		if (n_blocks < 0 || (n_blocks && !blocks)) throw std::runtime_error("pga_slice_blocks: null argument");
+		pga::slice_blocks_host(n_blocks, blocks, intervals, members, nodes, subs, dels, inss, out);
+		return 0;
+	} catch (std::exception &e) { pga_slice_free(out); set_err(e.what()); return -1; }
+}
+
 extern "C" int pga_stage_sort(int32_t n_seg, const uint64_t *seg_off, uint64_t *xy)
 {
 	try {
