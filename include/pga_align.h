@@ -340,7 +340,54 @@ typedef struct {
 int pga_slice_blocks(int64_t n_blocks, const pga_slice_block_t *blocks, const pga_slice_interval_t *intervals, const pga_rc_member_t *members, const pga_slice_node_t *nodes,
                      const pga_sub_t *subs, const pga_del_t *dels, const pga_ins_t *inss, pga_slice_out_t *out);
 void pga_slice_free(pga_slice_out_t *out);
-int pga_stats_version(void);     /* == PGA_STATS_VERSION of the header the library was built with */
+
+/* ---- back from a graph to its genomes: reconstruct (packages/pangraph/src/commands/reconstruct/reconstruct_run.rs:56-127) ----
+ * pga_reconstruct rebuilds the sequence of every path -- the whole of `pangraph reconstruct`, the check behind `pangraph build --verify`
+ * (build_run.rs:37-64, 174-178) and the debug check after every merge (build_run.rs:141-148) -- and, in verify mode, compares it on the
+ * device with the sequence the caller expects, so that only a verdict per path comes back.  Blocks, members and edits in the layout of
+ * pga_reconsensus (members numbered globally in block order); the nodes of path p are the next paths[p].n_nodes entries of nodes[].
+ * Per path, as the reference does it:
+ *   1. every node, in order: Edit::apply of its member's edits to the block's consensus (edits.rs:307-329, list-order rules as in
+ *      pga_reconsensus), reverse-complemented when nodes[].reverse != 0 (io/seq.rs:9-33: ACGTYRWSKMDVHBN- and nothing else, lower case is
+ *      rejected).  The letters of a forward node are not checked.  Two nodes may name the same member.
+ *   2. the concatenation must have paths[p].tot_len letters;
+ *   3. it is rotated right by first_pos (Vec::rotate_right: letter j moves to (j + first_pos) mod len); no other node's position is read,
+ *      and neither is `circular`;
+ *   4. a path without nodes is the empty sequence (tot_len and first_pos are not read).
+ * res[p].status, the first that applies (the reference's own order, this entry's refusal 3 behind the reference's Err 2):
+ *   0  built
+ *   2  a reverse node emits a letter the complement table rejects (the reference's Err)
+ *   3  a '-' would be emitted, from the consensus, an insertion or a substitution that no deletion hides: Edit::apply strips every '-'
+ *      (edits.rs:326) where pga_reconsensus and pga_solve_promises keep it; block sequences never hold one, so this entry does neither and refuses
+ *   1  the built length differs from tot_len (the reference's Err)
+ *   4  first_pos exceeds the built length (the reference panics)
+ *   5  verify mode only: the built length differs from expected_len[p]; nothing is compared
+ * A substitution under a deletion is never emitted and triggers neither 2 nor 3.  A path with status 1 or 4 is still built (unrotated),
+ * so that 2 and 3 are found.  The other paths of the call are not affected by any status.  res[p].len is always the built length.
+ * Write mode (out_seq != NULL): *out_seq is one malloc()ed buffer, freed with pga_free(); the sequence of a path with status 0 is
+ * (*out_seq)[seq_off .. seq_off + len) (every seq_off is a multiple of 16; the letters between two paths are padding).  A path with another
+ * status returns no letters: its seq_off is 0 and nothing is to be read for it.
+ * Verify mode (expected != NULL, and then expected_len != NULL): path p is compared with the expected_len[p] letters at expected[p] (not
+ * NUL-terminated).  first_mismatch is the index, in the final rotated sequence, of the first differing letter, or -1; n_mismatch the
+ * number of differing letters.  Both are -1 / 0 where status != 0.  No sequence is downloaded unless out_seq is given as well, and in
+ * verify-only mode none is stored on the device either.  Without verify mode first_mismatch is -1 and n_mismatch 0.
+ * Both modes may be given in one call; a call with neither fails.
+ * Malformed input fails the call (-1, message in pga_last_error(); nothing has run on the device by then): a NULL list with a non-zero
+ * count, a NULL consensus with a non-zero length, a consensus of 2^30 letters or more, an edit position or interval beyond its consensus
+ * (the rules of pga_solve_promises), a substitution letter outside one byte, a node whose member is out of range, a member or a path longer
+ * than 2^31 letters, a NULL expected[p] with a non-zero length.
+ * PGA_RECON_CHUNK_MB (default 2048) caps the built letters held on the device at once: paths are processed in chunks under it (a longer
+ * single path is a chunk of its own), `expected` is uploaded chunk by chunk, and of the graph only what the chunk's nodes read goes to
+ * the device: their runs (worked out on the host from the edits), the distinct consensus sequences and the insertion letters.  The result
+ * does not depend on the chunking.  Measurement: the kernel's intervals are logged as family 15 of pga_busy_begin / pga_busy_end.
+ * Returns 0, or -1 with the message in pga_last_error(). */
+typedef struct { uint64_t tot_len, first_pos; uint32_t n_nodes, pad; } pga_recon_path_t;   /* path.tot_len(), position().0 of the FIRST node, path.nodes.len() */
+typedef struct { uint64_t member; int32_t reverse, pad; } pga_recon_node_t;                 /* global index into members[]; strand().is_reverse() */
+typedef struct { int32_t status, pad; uint64_t len, seq_off; int64_t first_mismatch, n_mismatch; } pga_recon_res_t;
+int pga_reconstruct(int64_t n_blocks, const pga_rc_block_t *blocks, const pga_rc_member_t *members, const pga_sub_t *subs, const pga_del_t *dels,
+                    const pga_ins_t *inss, const char *ins_seq, int64_t n_paths, const pga_recon_path_t *paths, const pga_recon_node_t *nodes,
+                    const char *const *expected, const uint64_t *expected_len, pga_recon_res_t *res, char **out_seq);
+int pga_stats_version(void);    /* == PGA_STATS_VERSION of the header the library was built with */
 /* Measurement only (no reference interface behind it): the kern_ms sums of pga_stats_t count overlapping launches on different streams
  * and batches several times.  Between pga_busy_begin() and pga_busy_end() every event-bracketed launch of the process leaves its interval
  * on the device clock; pga_busy_end writes, for each of the PGA_N_KERNELS kernel families of pga_stats_t (same order), the length in ms of

@@ -994,6 +994,26 @@ extern "C" int pga_slice_blocks(int64_t n_blocks, const pga_slice_block_t *block
 	} catch (std::exception &e) { pga_slice_free(out); set_err(e.what()); return -1; }
 }
 
+// ---------------------------------------------------------------- reconstruct / verify (pga_reconstruct.hip)
+namespace pga {
+void reconstruct_host(int64_t n_blocks, const pga_rc_block_t *blocks, const pga_rc_member_t *members, const pga_sub_t *subs, const pga_del_t *dels, const pga_ins_t *inss,
+                      const char *ins_seq, int64_t n_paths, const pga_recon_path_t *paths, const pga_recon_node_t *nodes, const char *const *expected,
+                      const uint64_t *expected_len, pga_recon_res_t *res, char **out_seq);
+}
+extern "C" int pga_reconstruct(int64_t n_blocks, const pga_rc_block_t *blocks, const pga_rc_member_t *members, const pga_sub_t *subs, const pga_del_t *dels,
+                               const pga_ins_t *inss, const char *ins_seq, int64_t n_paths, const pga_recon_path_t *paths, const pga_recon_node_t *nodes,
+                               const char *const *expected, const uint64_t *expected_len, pga_recon_res_t *res, char **out_seq)
+{
+	if (out_seq) *out_seq = nullptr;
+	try {
+		require_device();
+		if (!expected && !out_seq) throw std::runtime_error("pga_reconstruct: neither write mode (out_seq) nor verify mode (expected) asked for");
+		if (n_blocks < 0 || (n_blocks && !blocks) || n_paths < 0) throw std::runtime_error("pga_reconstruct: null argument");
+		pga::reconstruct_host(n_blocks, blocks, members, subs, dels, inss, ins_seq, n_paths, paths, nodes, expected, expected_len, res, out_seq);
+		return 0;
+	} catch (std::exception &e) { set_err(e.what()); return -1; }
+}
+
 extern "C" int pga_stage_sort(int32_t n_seg, const uint64_t *seg_off, uint64_t *xy)
 {
 	try {

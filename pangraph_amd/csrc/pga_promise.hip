@@ -17,7 +17,7 @@
 // is a chunk of its own); results are packed per member in input order, so the output does not depend on the chunking.
 #include "pga_common.h"
 #include "../../include/pga_align.h"
-#include "pga_edits.h"
+#include "pga_runs.h"
 #include <exception>
 #include <thread>
 #include <unordered_map>
@@ -28,21 +28,7 @@ struct MvDevJob { uint64_t ref_off, qry_off; uint32_t ref_len, qry_len; int32_t 
 void map_variations_dev(int64_t n, const MvDevJob *jobs, const char *d_ascii, uint64_t cat_size, const pga_mapvar_params_t &prm, pga_mapvar_res_t *res,
                         std::vector<pga_sub_t> &h_subs, std::vector<pga_del_t> &h_dels, std::vector<pga_ins_t> &h_inss, std::vector<char> &h_seq, hipStream_t st);
 
-// io/seq.rs:9-29: ACGTYRWSKMDVHBN- and nothing else (0: rejected; lower case is rejected)
-struct CompTable { uint8_t t[256]; };
-constexpr CompTable make_comp_table()
-{
-	CompTable c{};
-	const char from[] = "ACGTYRWSKMDVHBN-", to[] = "TGCARYWSMKHBDVN-";
-	for (int i = 0; i < 16; ++i) c.t[(unsigned char)from[i]] = (uint8_t)to[i];
-	return c;
-}
-static constexpr CompTable h_comp = make_comp_table();
-__constant__ CompTable d_comp = make_comp_table();
-
-// one run of a member sequence: built letters [out, out of the next run) come from cons[src ..] (kind 0), ins_seq[src ..] (kind 1) or
-// are the one letter `src` (kind 2)
-struct PrSeg { uint32_t out, kind; uint64_t src; };
+// (the complement table, PrSeg -- one run of a member sequence -- and promise_segments: pga_runs.h)
 // dst: offset of the sequence in the ASCII buffer (a multiple of 4: a thread stores four letters at once); word0: the first of its words
 // among all words of the launch
 struct PrJob { uint64_t dst, seg_off, word0; uint32_t n_seg, len, reverse, pad; };
@@ -88,37 +74,6 @@ __global__ __launch_bounds__(PR_THREADS) void k_promise_build(const PrJob *__res
 
 // ---------------------------------------------------------------- host side
 struct PromiseStage { int32_t *status, *mean_shift; uint32_t *band_width; uint64_t *seq_off; std::vector<char> seqs; };
-
-// the runs of one prepared edit over a consensus of cons_len letters that starts at cons_base; returns the built length
-static uint32_t promise_segments(const PreparedEdit &P, uint32_t cons_len, uint64_t cons_base, uint64_t ins_base, std::vector<PrSeg> &out)
-{
-	uint32_t o = 0, p = 0;
-	size_t ii = 0, di = 0, si = 0;
-	auto copy_run = [&](uint32_t from, uint32_t to) {                     // consensus positions [from, to): none deleted, no insertion inside
-		while (si < P.subs.size() && P.subs[si].pos < from) ++si;           // substitutions of deleted positions
-		uint32_t q = from;
-		while (q < to) {
-			const uint32_t sp = si < P.subs.size() && P.subs[si].pos < to ? P.subs[si].pos : to;
-			if (sp > q) { out.push_back(PrSeg{o, 0u, cons_base + q}); o += sp - q; q = sp; }
-			if (q < to) {
-				while (si + 1 < P.subs.size() && P.subs[si + 1].pos == q) ++si;   // the last of equal positions wins (edits.rs:310-312)
-				out.push_back(PrSeg{o, 2u, (uint64_t)(P.subs[si].alt & 255u)}); ++o; ++q; ++si;
-			}
-		}
-	};
-	for (;;) {
-		for (; ii < P.inss.size() && P.inss[ii].pos == p; ++ii) if (P.inss[ii].len) { out.push_back(PrSeg{o, 1u, P.inss[ii].seq_off - ins_base}); o += P.inss[ii].len; }
-		if (p >= cons_len) break;
-		const uint32_t next = ii < P.inss.size() ? std::min(P.inss[ii].pos, cons_len) : cons_len;
-		while (p < next) {
-			while (di < P.dels.size() && P.dels[di].end <= p) ++di;
-			if (di < P.dels.size() && P.dels[di].start <= p) { p = std::min(P.dels[di].end, next); continue; }
-			const uint32_t stop = di < P.dels.size() ? std::min(P.dels[di].start, next) : next;
-			copy_run(p, stop); p = stop;
-		}
-	}
-	return o;
-}
 
 // what the host works out for one member before anything runs on the device
 struct PrMember { int32_t status; uint32_t len; int64_t ms, bw; std::vector<PrSeg> segs; };
