@@ -52,4 +52,34 @@ static uint32_t promise_segments(const PreparedEdit &P, uint32_t cons_len, uint6
 	return o;
 }
 
+// Edit::apply_aligned (edits.rs:331-347) as runs: besides PrSeg's kinds a GAP run (kind 3: n times '-', no source).  Over the prepared edit:
+// consensus runs, one-letter runs for the substitutions that survive (none under a deletion; of equal positions the last in list order,
+// which prepare_edit's stable sort keeps), one gap run per merged deletion interval; insertions are ignored.  Returns the built length,
+// counted run by run: the caller checks it against cons_len.
+constexpr uint32_t PR_GAP = 3;
+static uint32_t aligned_segments(const PreparedEdit &P, uint32_t cons_len, uint64_t cons_base, std::vector<PrSeg> &out)
+{
+	uint32_t o = 0, p = 0;
+	size_t di = 0, si = 0;
+	while (p < cons_len) {
+		while (di < P.dels.size() && P.dels[di].end <= p) ++di;
+		if (di < P.dels.size() && P.dels[di].start <= p) {                  // (merged intervals: the next one starts behind this one's end)
+			const uint32_t end = std::min(P.dels[di].end, cons_len);
+			out.push_back(PrSeg{o, PR_GAP, 0u}); o += end - p; p = end;
+			continue;
+		}
+		const uint32_t stop = di < P.dels.size() ? std::min(P.dels[di].start, cons_len) : cons_len;
+		while (si < P.subs.size() && P.subs[si].pos < p) ++si;              // substitutions of deleted positions
+		while (p < stop) {
+			const uint32_t sp = si < P.subs.size() && P.subs[si].pos < stop ? P.subs[si].pos : stop;
+			if (sp > p) { out.push_back(PrSeg{o, 0u, cons_base + p}); o += sp - p; p = sp; }
+			if (p < stop) {
+				while (si + 1 < P.subs.size() && P.subs[si + 1].pos == p) ++si;   // the last of equal positions wins (edits.rs:336-338)
+				out.push_back(PrSeg{o, 2u, (uint64_t)(P.subs[si].alt & 255u)}); ++o; ++p; ++si;
+			}
+		}
+	}
+	return o;
+}
+
 } // namespace pga
