@@ -25,6 +25,7 @@ inline dim3 threadIdx, blockIdx, blockDim, gridDim;
 #define __forceinline__ inline
 #define __restrict__
 #define __shared__ static
+#define __constant__
 #define __launch_bounds__(...)
 
 namespace emu {

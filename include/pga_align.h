@@ -387,13 +387,57 @@ typedef struct { int32_t status, pad; uint64_t len, seq_off; int64_t first_misma
 int pga_reconstruct(int64_t n_blocks, const pga_rc_block_t *blocks, const pga_rc_member_t *members, const pga_sub_t *subs, const pga_del_t *dels,
                     const pga_ins_t *inss, const char *ins_seq, int64_t n_paths, const pga_recon_path_t *paths, const pga_recon_node_t *nodes,
                     const char *const *expected, const uint64_t *expected_len, pga_recon_res_t *res, char **out_seq);
+
+/* ---- the exports of a finished graph, streamed: export block-sequences (pangraph_block.rs:135-189) and export core-genome
+ * (export_core_genome.rs:53-141) ----
+ * Both build ROWS of letters on the device from blocks, members and edits in the layout of pga_reconstruct and hand them to a SINK of the
+ * caller's tile by tile; the library keeps no row and downloads letters into its cached pinned blocks only.
+ *   pga_block_sequences  one row per member (global member order): aligned != 0: Edit::apply_aligned of its edits to the block's
+ *                        consensus (edits.rs:331-347: substitutions, then '-' at every deleted position, insertions missing; the row has
+ *                        cons_len letters); aligned == 0: Edit::apply WITHOUT the stripping of '-' (edits.rs:307-329, as pga_reconstruct).
+ *   pga_core_alignment   one row per path: the core blocks (Pangraph::core_block_ids, pangraph.rs:235-255: present exactly once in each
+ *                        path; member_path[m] is the path of global member m) in the order the guide nodes name them, each the sequence
+ *                        of the path's member of that block as above, reverse-complemented (io/seq.rs:9-33) where the guide node is
+ *                        reverse.  *core (malloc()ed, freed with pga_free(), *n_core entries) lists them with their first column.
+ * res[r] (r: the row's own index, whatever `order` is): len is the built length; status, the first that applies:
+ *   0  built
+ *   2  a reverse piece emits a letter the complement table rejects (the reference's Err)
+ *   3  unaligned mode only: a '-' is emitted, from the consensus, an insertion or a substitution (Edit::apply would strip it)
+ * order: NULL, or a permutation of the rows: they are built and delivered in that order (the record order of the reference's output, say).
+ * sink == NULL, verdict mode: statuses and lengths only, nothing but flags leaves the device.  A caller that must emit nothing when a row
+ * fails (the reference's export returns Err) calls this first.
+ * sink != NULL: called on the calling thread, once per tile of at most PGA_EXPORT_TILE_KB KB (default 16384; a multiple of 4, read at
+ * every call), tiles in delivery order: letters [row_off, row_off + n) of row segs[i].row are letters[segs[i].tile_off ..]; the segments of
+ * a call are in delivery order, exclude the padding between rows and empty rows, and over the calls tile every non-empty row exactly once.
+ * `letters` and `segs` are the library's and valid during the call only.  Letters are delivered AS BUILT, whatever the row's status
+ * turns out to be: res[] is complete when the entry returns.  A sink that returns non-zero stops the export: what is in flight is
+ * drained, no further call is made, the entry returns -1 ("sink stopped the export").
+ * PGA_EXPORT_RUNS_KB (default 262144, at least 1, read at every call) caps the run tables held at once: rows are processed in chunks under
+ * it (a single larger row is a chunk of its own).  Neither knob changes a result.
+ * Malformed input fails the call (-1, message in pga_last_error(); nothing has run on the device by then): what fails pga_reconstruct, a
+ * row over 2^31 letters, an `order` that is no permutation, a member_path or guide_path naming no path, a guide node whose member does
+ * not exist or is not on guide_path, a core block the guide nodes name twice or not at all.  n_paths == 0 gives no row and no core block.
+ * Measurement: the kernel's intervals are logged as family 16 of pga_busy_begin / pga_busy_end. */
+typedef struct { uint64_t row, row_off, tile_off; uint32_t n, pad; } pga_export_seg_t;
+typedef int (*pga_export_sink_t)(void *ctx, int64_t n_seg, const pga_export_seg_t *segs, const char *letters);
+typedef struct { int32_t status, pad; uint64_t len; } pga_export_res_t;
+typedef struct { uint32_t block; int32_t reverse; uint64_t col; uint32_t cons_len, pad; } pga_core_block_t;   /* col: the first column of the block in every row */
+int pga_block_sequences(int64_t n_blocks, const pga_rc_block_t *blocks, const pga_rc_member_t *members, const pga_sub_t *subs, const pga_del_t *dels,
+                        const pga_ins_t *inss, const char *ins_seq, int aligned, const uint64_t *order, pga_export_res_t *res /* one per member */,
+                        pga_export_sink_t sink, void *ctx);
+int pga_core_alignment(int64_t n_blocks, const pga_rc_block_t *blocks, const pga_rc_member_t *members, const pga_sub_t *subs, const pga_del_t *dels,
+                       const pga_ins_t *inss, const char *ins_seq, const uint32_t *member_path, int64_t n_paths, int64_t guide_path, int64_t n_guide_nodes,
+                       const pga_recon_node_t *guide_nodes, int aligned, const uint64_t *order, pga_export_res_t *res /* one per path */,
+                       pga_core_block_t **core, int64_t *n_core, pga_export_sink_t sink, void *ctx);
 int pga_stats_version(void);    /* == PGA_STATS_VERSION of the header the library was built with */
 /* Measurement only (no reference interface behind it): the kern_ms sums of pga_stats_t count overlapping launches on different streams
  * and batches several times.  Between pga_busy_begin() and pga_busy_end() every event-bracketed launch of the process leaves its interval
  * on the device clock; pga_busy_end writes, for each of the PGA_N_KERNELS kernel families of pga_stats_t (same order), the length in ms of
  * the UNION of its intervals, and in busy_ms[PGA_N_KERNELS] the union over all families (n >= PGA_N_KERNELS + 1).  Returns the number of
- * intervals seen, -1 on error. */
+ * intervals seen, -1 on error.  Families that pga_stats_t does not count follow the union where n has room for them: busy_ms[PGA_N_KERNELS + 1 + j]
+ * is family PGA_N_KERNELS + j, j < PGA_N_BUSY_EXTRA (family 16: k_export_rows). */
 #define PGA_N_KERNELS 16
+#define PGA_N_BUSY_EXTRA 1
 int pga_busy_begin(void);
 int pga_busy_end(double *busy_ms, int32_t n);
 #ifdef __cplusplus

@@ -724,6 +724,7 @@ extern "C" int pga_busy_end(double *busy_ms, int32_t n)
 	};
 	for (int k = 0; k < PGA_N_KERNELS; ++k) busy_ms[k] = union_ms(k);
 	busy_ms[PGA_N_KERNELS] = union_ms(-1);
+	for (int j = 0; j < PGA_N_BUSY_EXTRA && PGA_N_KERNELS + 1 + j < n; ++j) busy_ms[PGA_N_KERNELS + 1 + j] = union_ms(PGA_N_KERNELS + j);
 	return (int)iv.size();
 }
 
@@ -1028,6 +1029,38 @@ extern "C" int pga_stage_sort(int32_t n_seg, const uint64_t *seg_off, uint64_t *
 		DBuf<uint32_t> df; df.upload(flag, 0);
 		replay_sort_segments(a.p, n, off.p, dl.p, n_seg, df.p, 0);
 		if (n) { PGA_HIP(hipMemcpyAsync(xy, a.p, n * sizeof(u128), hipMemcpyDeviceToHost, 0)); PGA_HIP(sync_stream(0)); }
+		return 0;
+	} catch (std::exception &e) { set_err(e.what()); return -1; }
+}
+
+// ---------------------------------------------------------------- the exports of a finished graph (pga_export.hip)
+namespace pga {
+void block_sequences_host(int64_t n_blocks, const pga_rc_block_t *blocks, const pga_rc_member_t *members, const pga_sub_t *subs, const pga_del_t *dels, const pga_ins_t *inss,
+                          const char *ins_seq, int aligned, const uint64_t *order, pga_export_res_t *res, pga_export_sink_t sink, void *ctx);
+void core_alignment_host(int64_t n_blocks, const pga_rc_block_t *blocks, const pga_rc_member_t *members, const pga_sub_t *subs, const pga_del_t *dels, const pga_ins_t *inss,
+                         const char *ins_seq, const uint32_t *member_path, int64_t n_paths, int64_t guide_path, int64_t n_guide_nodes, const pga_recon_node_t *guide_nodes,
+                         int aligned, const uint64_t *order, pga_export_res_t *res, pga_core_block_t **core_out, int64_t *n_core_out, pga_export_sink_t sink, void *ctx);
+}
+extern "C" int pga_block_sequences(int64_t n_blocks, const pga_rc_block_t *blocks, const pga_rc_member_t *members, const pga_sub_t *subs, const pga_del_t *dels,
+                                   const pga_ins_t *inss, const char *ins_seq, int aligned, const uint64_t *order, pga_export_res_t *res, pga_export_sink_t sink, void *ctx)
+{
+	try {
+		require_device();
+		pga::block_sequences_host(n_blocks, blocks, members, subs, dels, inss, ins_seq, aligned, order, res, sink, ctx);
+		return 0;
+	} catch (std::exception &e) { set_err(e.what()); return -1; }
+}
+extern "C" int pga_core_alignment(int64_t n_blocks, const pga_rc_block_t *blocks, const pga_rc_member_t *members, const pga_sub_t *subs, const pga_del_t *dels,
+                                  const pga_ins_t *inss, const char *ins_seq, const uint32_t *member_path, int64_t n_paths, int64_t guide_path, int64_t n_guide_nodes,
+                                  const pga_recon_node_t *guide_nodes, int aligned, const uint64_t *order, pga_export_res_t *res, pga_core_block_t **core, int64_t *n_core,
+                                  pga_export_sink_t sink, void *ctx)
+{
+	if (core) *core = nullptr;
+	if (n_core) *n_core = 0;
+	try {
+		require_device();
+		if (!core || !n_core) throw std::runtime_error("pga_core_alignment: null argument");
+		pga::core_alignment_host(n_blocks, blocks, members, subs, dels, inss, ins_seq, member_path, n_paths, guide_path, n_guide_nodes, guide_nodes, aligned, order, res, core, n_core, sink, ctx);
 		return 0;
 	} catch (std::exception &e) { set_err(e.what()); return -1; }
 }

@@ -1,5 +1,5 @@
 // pga_runs.h -- a member sequence as a chain of RUNS, and the complement table: what the entries that build sequences on the device from a
-// consensus and an edit list share (pga_promise.hip: the members of a merge promise; pga_reconstruct.hip: the nodes of a path).
+// consensus and an edit list share (pga_promise.hip: the members of a merge promise; pga_reconstruct.hip: the nodes of a path; pga_export_rows.h: the pieces of an exported row).
 #pragma once
 #include "pga_edits.h"
 
