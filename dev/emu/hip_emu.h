@@ -1,7 +1,7 @@
 // hip_emu.h -- barrier-synchronous HIP kernels on the host (development and CPU tests; g++ -std=c++17 -DPGA_EMU).
 //
 // There is no GPU in the build container.  A kernel that only uses threadIdx / blockIdx / blockDim, __shared__ arrays, __syncthreads() and
-// atomicAdd / atomicMax / atomicOr (no wave intrinsics, no inline assembly) means the same thing when every thread of a workgroup is a FIBER and
+// atomicAdd / atomicMax / atomicMin / atomicOr (no wave intrinsics, no inline assembly) means the same thing when every thread of a workgroup is a FIBER and
 // __syncthreads() hands control to the next one: a workgroup runs phase by phase (every thread up to its next barrier, then every thread up to the
 // one after), workgroups run one after the other, `__shared__` becomes a function-local static (one workgroup at a time, contents undefined at
 // kernel entry as on the device).  This checks the LOGIC of such a kernel -- indexing, barrier placement (threads of a workgroup that leave a kernel
@@ -40,6 +40,7 @@ inline void __syncthreads() { emu::cur->at_barrier = true; swapcontext(&emu::cur
 template <class T> inline T atomicAdd(T *p, T v) { const T o = *p; *p = o + v; return o; }
 template <class T> inline T atomicOr(T *p, T v) { const T o = *p; *p = o | v; return o; }
 template <class T> inline T atomicMax(T *p, T v) { const T o = *p; if (o < v) *p = v; return o; }
+template <class T> inline T atomicMin(T *p, T v) { const T o = *p; if (v < o) *p = v; return o; }
 
 template <class F> inline void emu_launch(dim3 grid, dim3 block, F kernel_call)
 {

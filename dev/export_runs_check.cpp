@@ -1,6 +1,6 @@
 // export_runs_check.cpp -- the arithmetic of the aligned run builder (aligned_segments, pangraph_amd/csrc/pga_runs.h) without a device:
-// random edits are prepared (prepare_edit), turned into runs, the runs listed forward and -- as pga_reconstruct.hip lists a node on the
-// reverse strand -- backwards, and a scalar walk of each table (letter by letter, as k_reconstruct steps from run to run) is compared with a direct
+// random edits are prepared (prepare_edit), turned into runs, the runs listed forward and -- as row_piece_runs (pga_rows.h) lists a piece on the
+// reverse strand -- backwards, and a scalar walk of each table (letter by letter, as k_rows steps from run to run) is compared with a direct
 // Edit::apply_aligned (edits.rs:331-347) and its reverse complement.  Shapes: substitutions under deletions, duplicate positions,
 // overlapping and adjacent deletions, deletions of the whole consensus, consensus lengths around 16.
 // Build and run (host only):  g++ -std=c++17 -g -fsanitize=address,undefined -fno-sanitize-recover=undefined -Ipangraph_amd/csrc -Iinclude
@@ -13,7 +13,7 @@
 
 using namespace pga;
 
-struct Run { uint32_t out, kind; uint64_t src; };                      // as RcRun of pga_reconstruct.hip, plus the gap kind: kind | 4 = read backwards and complement
+struct Run { uint32_t out, kind; uint64_t src; };                      // as RowRun of pga_rows.h: kind | 4 = read backwards and complement
 
 static std::string walk(const std::vector<Run> &R, uint32_t len, const std::string &cons, bool &bad)
 {

@@ -435,7 +435,7 @@ int pga_stats_version(void);    /* == PGA_STATS_VERSION of the header the librar
  * on the device clock; pga_busy_end writes, for each of the PGA_N_KERNELS kernel families of pga_stats_t (same order), the length in ms of
  * the UNION of its intervals, and in busy_ms[PGA_N_KERNELS] the union over all families (n >= PGA_N_KERNELS + 1).  Returns the number of
  * intervals seen, -1 on error.  Families that pga_stats_t does not count follow the union where n has room for them: busy_ms[PGA_N_KERNELS + 1 + j]
- * is family PGA_N_KERNELS + j, j < PGA_N_BUSY_EXTRA (family 16: k_export_rows). */
+ * is family PGA_N_KERNELS + j, j < PGA_N_BUSY_EXTRA (family 16: k_rows<false> of the exports). */
 #define PGA_N_KERNELS 16
 #define PGA_N_BUSY_EXTRA 1
 int pga_busy_begin(void);

@@ -215,6 +215,7 @@ void busy_note(int kern, hipEvent_t a, hipEvent_t b);
 // leased non-blocking streams of the current device (pga_mem.cpp); release drains the stream
 hipStream_t stream_lease();
 void stream_release(hipStream_t s);
+struct StreamLease { hipStream_t s; StreamLease() : s(stream_lease()) {} ~StreamLease() { stream_release(s); } StreamLease(const StreamLease&) = delete; StreamLease &operator=(const StreamLease&) = delete; };
 // times everything enqueued on `st` between construction and stop()
 // (mark() closes the interval without waiting; finish() reads it -- behind a synchronisation the caller needs anyway it costs nothing, where stop()
 // makes the host wait for the kernels it has just queued before it may queue the next ones)

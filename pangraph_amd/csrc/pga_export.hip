@@ -1,9 +1,9 @@
 // pga_export.hip -- the two exports of a finished graph on the device, streamed: pga_block_sequences (export block-sequences,
 // PangraphBlock::sequences, pangraph_block.rs:135-189: one row per member) and pga_core_alignment (export core-genome, core_block_aln with
 // concatenate_records, export_core_genome.rs:53-141: one row per path, its pieces the core blocks in guide order with the guide's strand).
-// The row table and the kernel are pga_export_rows.h.  What runs where:
+// The row table and the kernel are pga_rows.h.  What runs where:
 //   host     validation and the core selection (all of it before anything is launched), the row tables, chunk by chunk
-//   device   k_export_rows over the unit space of a chunk
+//   device   k_rows<false> over the unit space of a chunk
 // Rows are taken in delivery order (`order`, or their own) and grouped into CHUNKS whose run tables stay under PGA_EXPORT_RUNS_KB (default
 // 262144; a single larger row is a chunk of its own).  Per chunk the device receives the runs, one copy of every consensus a piece reads and
 // the slice of the insertion letters the pieces point into.
@@ -17,7 +17,7 @@
 // Neither knob changes a result.
 #include "pga_common.h"
 #include "../../include/pga_align.h"
-#include "pga_export_rows.h"
+#include "pga_rows.h"
 
 namespace pga {
 
@@ -36,13 +36,12 @@ static uint64_t ex_knob_kb(const std::string &who, const char *name, uint64_t df
 }
 
 namespace {
-struct ExStream { hipStream_t s; ExStream() : s(stream_lease()) {} ~ExStream() { stream_release(s); } };       // (release drains the stream)
 struct ExEvent { hipEvent_t e = nullptr; ExEvent() { PGA_HIP(hipEventCreate(&e)); } ~ExEvent() { (void)hipEventDestroy(e); } };
 struct ExPin { char *p = nullptr; uint64_t cap = 0; ~ExPin() { pin_free(p); } };
 }
 
 // rows[r] = pieces[piece_first[r] .. piece_first[r + 1]); res[r] for every row; rows are built and delivered in `order`
-static void export_rows(const std::string &who, const ExGraph &G, uint64_t n_rows, const std::vector<uint64_t> &piece_first, const std::vector<ExPiece> &pieces,
+static void export_rows(const std::string &who, const RowGraph &G, uint64_t n_rows, const std::vector<uint64_t> &piece_first, const std::vector<RowPiece> &pieces,
                         const uint64_t *order, pga_export_res_t *res, pga_export_sink_t sink, void *ctx)
 {
 	auto fail = [&](const std::string &what) { throw std::runtime_error(who + ": " + what); };
@@ -60,19 +59,19 @@ static void export_rows(const std::string &who, const ExGraph &G, uint64_t n_row
 		for (uint64_t q = piece_first[r]; q < piece_first[r + 1]; ++q) { l += G.mem_len[pieces[q].member]; if (l > (1ULL << 31)) fail("row over 2^31 letters (row " + std::to_string(r) + ")"); }
 		res[r].status = 0; res[r].pad = 0; res[r].len = l;
 	}
-	const uint64_t tile_units = ex_knob_kb(who, "PGA_EXPORT_TILE_KB", 16384, 4) * 1024 / EX_LETTERS;
-	const uint64_t runs_cap = ex_knob_kb(who, "PGA_EXPORT_RUNS_KB", 262144, 1) * 1024 / sizeof(ExRun);
-	const uint32_t gap_flag = G.aligned ? 0u : EX_GAP;
+	const uint64_t tile_units = ex_knob_kb(who, "PGA_EXPORT_TILE_KB", 16384, 4) * 1024 / ROW_LETTERS;
+	const uint64_t runs_cap = ex_knob_kb(who, "PGA_EXPORT_RUNS_KB", 262144, 1) * 1024 / sizeof(RowRun);
+	const uint32_t gap_flag = G.aligned ? 0u : ROW_GAP;
 
 	// (declared before the streams: the streams are drained first when the scope is left, by a throw too)
 	DBuf<char> d_cons, d_iseq, d_tile[2];
-	DBuf<ExJob> d_jobs; DBuf<ExRun> d_runs; DBuf<uint32_t> d_flags;
+	DBuf<RowJob> d_jobs; DBuf<RowRun> d_runs; DBuf<uint32_t> d_flags;
 	ExPin pin[2];
-	ExTable T; PreparedEdit P; std::vector<PrSeg> segs_scratch;
+	RowTable T; PreparedEdit P; std::vector<PrSeg> segs_scratch;
 	std::vector<pga_export_seg_t> segs;
 	std::vector<uint32_t> flags;
 	ExEvent ev_ka[2], ev_kb[2], ev_c[2];                                  // per tile buffer: before and behind its kernel, behind its copy
-	ExStream s_kern, s_copy;
+	StreamLease s_kern, s_copy;                                           // (release drains the stream)
 	const hipStream_t sk = s_kern.s, sc = s_copy.s;
 
 	uint64_t k = 0;
@@ -81,8 +80,8 @@ static void export_rows(const std::string &who, const ExGraph &G, uint64_t n_row
 		T.clear();
 		for (uint64_t in_chunk = 0; k < n_rows; ++k, ++in_chunk) {
 			const uint64_t r = order ? order[k] : k;
-			const ExTable::Mark mk = T.mark();
-			ex_append_row(G, r, pieces.data() + piece_first[r], piece_first[r + 1] - piece_first[r], T, P, segs_scratch);
+			const RowTable::Mark mk = T.mark();
+			row_append_row(G, r, pieces.data() + piece_first[r], piece_first[r + 1] - piece_first[r], T, P, segs_scratch);
 			if (T.runs.size() > runs_cap && in_chunk) { T.undo(mk); break; }
 		}
 		if (T.jobs.empty()) continue;
@@ -95,14 +94,14 @@ static void export_rows(const std::string &who, const ExGraph &G, uint64_t n_row
 		d_jobs.upload(T.jobs, sk); d_runs.upload(T.runs, sk);
 		d_flags.alloc(n_jobs); d_flags.zero(sk);
 		if (!sink) {
-			const unsigned grid = (unsigned)std::min<uint64_t>((units + EX_THREADS - 1) / EX_THREADS, 2048);
+			const unsigned grid = (unsigned)std::min<uint64_t>((units + ROW_THREADS - 1) / ROW_THREADS, 2048);
 			EventTimer et(sk);
-			hipLaunchKernelGGL(k_export_rows, dim3(grid), dim3(EX_THREADS), 0, sk, d_jobs.p, (int)n_jobs, (uint64_t)0, units, d_runs.p, d_cons.p, d_iseq.p, ins_lo,
-			                   (char*)nullptr, d_flags.p, gap_flag);
+			hipLaunchKernelGGL(k_rows<false>, dim3(grid), dim3(ROW_THREADS), 0, sk, d_jobs.p, (int)n_jobs, (uint64_t)0, units, d_runs.p, d_cons.p, d_iseq.p, ins_lo,
+			                   (char*)nullptr, d_flags.p, gap_flag, (const char*)nullptr, (unsigned long long*)nullptr, (unsigned long long*)nullptr);
 			PGA_HIP(hipGetLastError());
 			et.finish(EX_BUSY_FAMILY);
 		} else {
-			const uint64_t n_tiles = (units + tile_units - 1) / tile_units, tile_bytes = std::min(units, tile_units) * EX_LETTERS;
+			const uint64_t n_tiles = (units + tile_units - 1) / tile_units, tile_bytes = std::min(units, tile_units) * ROW_LETTERS;
 			for (int b = 0; b < (n_tiles > 1 ? 2 : 1); ++b) {                   // (nothing of an earlier chunk is in flight any more)
 				d_tile[b].alloc(tile_bytes);
 				if (pin[b].cap < tile_bytes) { pin_free(pin[b].p); pin[b].p = nullptr; pin[b].cap = 0; pin[b].p = (char*)pin_alloc(tile_bytes); pin[b].cap = tile_bytes; }
@@ -112,8 +111,8 @@ static void export_rows(const std::string &who, const ExGraph &G, uint64_t n_row
 				uint64_t a, z; span(t, a, z);
 				const int b = (int)(t & 1);
 				PGA_HIP(hipEventRecord(ev_ka[b].e, sk));
-				hipLaunchKernelGGL(k_export_rows, dim3((unsigned)((z - a + EX_THREADS - 1) / EX_THREADS)), dim3(EX_THREADS), 0, sk, d_jobs.p, (int)n_jobs, a, z, d_runs.p,
-				                   d_cons.p, d_iseq.p, ins_lo, d_tile[b].p, d_flags.p, gap_flag);
+				hipLaunchKernelGGL(k_rows<false>, dim3((unsigned)((z - a + ROW_THREADS - 1) / ROW_THREADS)), dim3(ROW_THREADS), 0, sk, d_jobs.p, (int)n_jobs, a, z, d_runs.p,
+				                   d_cons.p, d_iseq.p, ins_lo, d_tile[b].p, d_flags.p, gap_flag, (const char*)nullptr, (unsigned long long*)nullptr, (unsigned long long*)nullptr);
 				PGA_HIP(hipGetLastError());
 				PGA_HIP(hipEventRecord(ev_kb[b].e, sk));
 			};
@@ -122,11 +121,11 @@ static void export_rows(const std::string &who, const ExGraph &G, uint64_t n_row
 				uint64_t a, z; span(t, a, z);
 				segs.clear();
 				while (jc < n_jobs) {
-					const ExJob &J = T.jobs[jc];
+					const RowJob &J = T.jobs[jc];
 					if (J.unit0 >= z) break;
-					const uint64_t from = std::max(J.unit0, a), row_off = (from - J.unit0) * EX_LETTERS, row_end = std::min<uint64_t>(J.len, (z - J.unit0) * EX_LETTERS);
-					segs.push_back(pga_export_seg_t{T.job_row[jc], row_off, (from - a) * EX_LETTERS, (uint32_t)(row_end - row_off), 0u});
-					if (J.unit0 + ex_pad(J.len) / EX_LETTERS > z) break;              // the row goes on in the next tile
+					const uint64_t from = std::max(J.unit0, a), row_off = (from - J.unit0) * ROW_LETTERS, row_end = std::min<uint64_t>(J.len, (z - J.unit0) * ROW_LETTERS);
+					segs.push_back(pga_export_seg_t{T.job_row[jc], row_off, (from - a) * ROW_LETTERS, (uint32_t)(row_end - row_off), 0u});
+					if (J.unit0 + row_pad(J.len) / ROW_LETTERS > z) break;              // the row goes on in the next tile
 					++jc;
 				}
 				if (sink(ctx, (int64_t)segs.size(), segs.data(), pin[t & 1].p) != 0) {
@@ -143,7 +142,7 @@ static void export_rows(const std::string &who, const ExGraph &G, uint64_t n_row
 				uint64_t a, z; span(t, a, z);
 				const int b = (int)(t & 1);
 				PGA_HIP(hipStreamWaitEvent(sc, ev_kb[b].e, 0));
-				PGA_HIP(hipMemcpyAsync(pin[b].p, d_tile[b].p, (z - a) * EX_LETTERS, hipMemcpyDeviceToHost, sc));   // (the sink of tile t-2 has returned)
+				PGA_HIP(hipMemcpyAsync(pin[b].p, d_tile[b].p, (z - a) * ROW_LETTERS, hipMemcpyDeviceToHost, sc));   // (the sink of tile t-2 has returned)
 				PGA_HIP(hipEventRecord(ev_c[b].e, sc));
 				if (t >= 1) copied(t - 1);
 				if (t + 1 < n_tiles) launch(t + 1);                               // (into the device tile of t-1, whose copy is complete)
@@ -158,7 +157,7 @@ static void export_rows(const std::string &who, const ExGraph &G, uint64_t n_row
 			dl.wait();
 		}
 		PGA_HIP(sync_stream(sk));                                             // (the chunk's host tables may go)
-		for (size_t j = 0; j < n_jobs; ++j) res[T.job_row[j]].status = (flags[j] & EX_BAD_COMP) ? 2 : (flags[j] & EX_GAP) ? 3 : 0;
+		for (size_t j = 0; j < n_jobs; ++j) res[T.job_row[j]].status = (flags[j] & ROW_BAD_COMP) ? 2 : (flags[j] & ROW_GAP) ? 3 : 0;
 	}
 }
 
@@ -166,11 +165,11 @@ void block_sequences_host(int64_t n_blocks, const pga_rc_block_t *blocks, const 
                           const char *ins_seq, int aligned, const uint64_t *order, pga_export_res_t *res, pga_export_sink_t sink, void *ctx)
 {
 	const std::string who = "pga_block_sequences";
-	ExGraph G;
-	ex_graph_init(G, who, n_blocks, blocks, members, subs, dels, inss, ins_seq, aligned != 0);
+	RowGraph G;
+	row_graph_init(G, who, n_blocks, blocks, members, subs, dels, inss, ins_seq, aligned != 0, 1);
 	std::vector<uint64_t> piece_first(G.n_mem + 1);
-	std::vector<ExPiece> pieces(G.n_mem);
-	for (uint64_t m = 0; m < G.n_mem; ++m) { piece_first[m] = m; pieces[m] = ExPiece{m, 0u, 0u}; }
+	std::vector<RowPiece> pieces(G.n_mem);
+	for (uint64_t m = 0; m < G.n_mem; ++m) { piece_first[m] = m; pieces[m] = RowPiece{m, 0u, 0u}; }
 	piece_first[G.n_mem] = G.n_mem;
 	export_rows(who, G, G.n_mem, piece_first, pieces, order, res, sink, ctx);
 }
@@ -181,12 +180,12 @@ void core_alignment_host(int64_t n_blocks, const pga_rc_block_t *blocks, const p
 {
 	const std::string who = "pga_core_alignment";
 	auto fail = [&](const std::string &what) { throw std::runtime_error(who + ": " + what); };
-	ExGraph G;
-	ex_graph_init(G, who, n_blocks, blocks, members, subs, dels, inss, ins_seq, aligned != 0);
+	RowGraph G;
+	row_graph_init(G, who, n_blocks, blocks, members, subs, dels, inss, ins_seq, aligned != 0, 1);
 	if (n_paths < 0 || n_guide_nodes < 0) fail("negative count");
 	std::vector<pga_core_block_t> core;
 	std::vector<uint64_t> piece_first((size_t)n_paths + 1, 0);
-	std::vector<ExPiece> pieces;
+	std::vector<RowPiece> pieces;
 	if (n_paths > 0) {
 		if (n_paths >= (1LL << 32)) fail("more than 2^32 paths");
 		if (G.n_mem && !member_path) fail("null member_path");
@@ -220,7 +219,7 @@ void core_alignment_host(int64_t n_blocks, const pga_rc_block_t *blocks, const p
 		pieces.resize(core.size() * (size_t)n_paths);
 		for (size_t c = 0; c < core.size(); ++c)
 			for (uint64_t m = G.mem_first[core[c].block]; m < G.mem_first[core[c].block + 1]; ++m)
-				pieces[(size_t)member_path[m] * core.size() + c] = ExPiece{m, (uint32_t)core[c].reverse, 0u};
+				pieces[(size_t)member_path[m] * core.size() + c] = RowPiece{m, (uint32_t)core[c].reverse, 0u};
 		for (int64_t p = 0; p <= n_paths; ++p) piece_first[p] = (uint64_t)p * core.size();
 	}
 	export_rows(who, G, (uint64_t)n_paths, piece_first, pieces, order, res, sink, ctx);

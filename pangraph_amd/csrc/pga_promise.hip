@@ -18,8 +18,6 @@
 #include "pga_common.h"
 #include "../../include/pga_align.h"
 #include "pga_runs.h"
-#include <exception>
-#include <thread>
 #include <unordered_map>
 
 namespace pga {
@@ -130,7 +128,7 @@ void solve_promises_host(int64_t n_promises, const pga_promise_t *promises, cons
 	if (stage) stage->seq_off[0] = 0;
 	o_subs.clear(); o_dels.clear(); o_inss.clear(); o_iseq.clear();
 	const size_t chunk_cap = promise_chunk_bytes();
-	const int n_threads = (int)std::min<unsigned>(8, std::max(1u, std::thread::hardware_concurrency()));
+	const int n_threads = range_threads();
 	std::vector<PrMember> pm;
 	int64_t p0 = 0;
 	while (p0 < n_promises) {
@@ -195,16 +193,7 @@ void solve_promises_host(int64_t n_promises, const pga_promise_t *promises, cons
 				M.ms = ms + cband[p].ms; M.bw = bw + cband[p].bw;                  // map_variations.rs:23-26
 			}
 		};
-		{
-			const uint64_t n = m1 - m0, per = (n + (uint64_t)n_threads - 1) / (uint64_t)n_threads;
-			std::vector<std::thread> th; std::vector<std::exception_ptr> err((size_t)n_threads);
-			if (n < 64) work(m0, m1);
-			else {
-				for (int t = 0; t < n_threads; ++t) th.emplace_back([&, t]() { try { work(m0 + std::min(n, per * t), m0 + std::min(n, per * (t + 1))); } catch (...) { err[t] = std::current_exception(); } });
-				for (auto &x : th) x.join();
-				for (auto &e : err) if (e) std::rethrow_exception(e);
-			}
-		}
+		thread_ranges(m1 - m0, n_threads, [&](int, uint64_t a, uint64_t z) { work(m0 + a, m0 + z); });
 		// ---- the device's ASCII buffer: anchors first, then every non-empty member sequence at a multiple of four ----
 		std::vector<PrJob> jobs; std::vector<uint64_t> job_member; std::vector<PrSeg> segs;
 		uint64_t cat = (h_anchor.size() + 3) & ~(uint64_t)3, words = 0;

@@ -1,9 +1,25 @@
 // pga_runs.h -- a member sequence as a chain of RUNS, and the complement table: what the entries that build sequences on the device from a
-// consensus and an edit list share (pga_promise.hip: the members of a merge promise; pga_reconstruct.hip: the nodes of a path; pga_export_rows.h: the pieces of an exported row).
+// consensus and an edit list share (pga_promise.hip: the members of a merge promise; pga_rows.h: the pieces of a row -- the nodes of a path for
+// pga_reconstruct.hip, the pieces of an exported row for pga_export.hip), and the host threads their list bookkeeping runs on.
 #pragma once
 #include "pga_edits.h"
+#include <exception>
+#include <thread>
 
 namespace pga {
+
+// f(t, a, z) over [0, n) in contiguous ranges on a few host threads (range t is the t-th in order; under 64 items: inline, as range 0);
+// exceptions are passed on
+static inline int range_threads() { return (int)std::min<unsigned>(8, std::max(1u, std::thread::hardware_concurrency())); }
+template <class F> static void thread_ranges(uint64_t n, int n_threads, F f)
+{
+	if (n < 64 || n_threads <= 1) { f(0, (uint64_t)0, n); return; }
+	const uint64_t per = (n + (uint64_t)n_threads - 1) / (uint64_t)n_threads;
+	std::vector<std::thread> th; std::vector<std::exception_ptr> err((size_t)n_threads);
+	for (int t = 0; t < n_threads; ++t) th.emplace_back([&, t]() { try { f(t, std::min(n, per * t), std::min(n, per * (t + 1))); } catch (...) { err[t] = std::current_exception(); } });
+	for (auto &x : th) x.join();
+	for (auto &e : err) if (e) std::rethrow_exception(e);
+}
 
 // io/seq.rs:9-29: ACGTYRWSKMDVHBN- and nothing else (0: rejected; lower case is rejected)
 struct CompTable { uint8_t t[256]; };

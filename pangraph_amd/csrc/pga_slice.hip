@@ -406,7 +406,7 @@ void slice_blocks_host(int64_t n_blocks, const pga_slice_block_t *blocks, const 
 		return;
 	}
 	// ---- the device ----
-	struct Stream { hipStream_t s; Stream() : s(stream_lease()) {} ~Stream() { stream_release(s); } } stream;
+	StreamLease stream;
 	hipStream_t st = stream.s;
 	DBuf<SlBlk> d_blk; d_blk.upload(blk, st);
 	DBuf<SlMem> d_mem; d_mem.upload(mem, st);

@@ -10,7 +10,7 @@ from . import batch
 from .mapvar import del_t, ins_t, sub_t
 from .reconsensus import rc_block_t, rc_member_t
 
-TILE = 4096          # letters one workgroup of k_reconstruct writes (256 threads x 16 letters, pga_reconstruct.hip)
+TILE = 4096          # letters one workgroup of k_rows writes (256 threads x 16 letters, pga_rows.h)
 LETTERS = 16         # letters one thread writes; every path starts at a multiple of it in the output
 
 

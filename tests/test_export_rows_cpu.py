@@ -1,4 +1,4 @@
-"""pga_export_rows.h without a GPU: the host row-table builder and k_export_rows under dev/emu/hip_emu.h, in a stand-alone program under the
+"""pga_rows.h without a GPU: the host row-table builder and k_rows (both instantiations) under dev/emu/hip_emu.h, in a stand-alone program under the
 address and undefined-behaviour sanitizers (tests/emu/export_rows_emu.cpp), and what the GPU tests rely on their generated graphs for
 (tests/export_gen.py), by the restatement tests/export_ref.py alone."""
 import os
@@ -19,7 +19,7 @@ def test_export_rows_under_emulation_and_sanitizers(tmp_path):
     if not cxx:
         pytest.skip("no host compiler")
     exe = str(tmp_path / "export_rows_emu")
-    subprocess.run([cxx, "-std=c++17", "-g1", "-O0", "-DPGA_EMU", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
+    subprocess.run([cxx, "-std=c++17", "-g1", "-O0", "-DPGA_EMU", "-pthread", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
                     os.path.join(ROOT, "tests", "emu", "export_rows_emu.cpp"), "-o", exe], check=True, capture_output=True, text=True)
     r = subprocess.run([exe], capture_output=True, text=True)
     # (the one line the address sanitizer prints about swapcontext, which the emulator's fibers use, is no finding)
