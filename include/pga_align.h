@@ -429,6 +429,46 @@ int pga_core_alignment(int64_t n_blocks, const pga_rc_block_t *blocks, const pga
                        const pga_ins_t *inss, const char *ins_seq, const uint32_t *member_path, int64_t n_paths, int64_t guide_path, int64_t n_guide_nodes,
                        const pga_recon_node_t *guide_nodes, int aligned, const uint64_t *order, pga_export_res_t *res /* one per path */,
                        pga_core_block_t **core, int64_t *n_core, pga_export_sink_t sink, void *ctx);
+
+/* ---- simplify: the block concatenations of remove_transitive_edges (packages/pangraph/src/circularize/merge_blocks.rs:92-148) ----
+ * pga_merge_blocks performs any number of independent concatenations in one call: per edge concatenate_alignments of the left and the right
+ * block, each taken as it is or through PangraphBlock::reverse_complement (pangraph_block.rs:63-75) first.  orient_merging_edge,
+ * find_node_pairings, the node ids and the path / node updates stay with the caller (pangraph_amd/simplify.py).  Blocks, members and edits
+ * in the layout of pga_reconstruct; a block may be named by several edges, inputs are only read.
+ * partner: for edge e the next blocks[left].n_members entries; entry k is the index, inside the right block, of the member joined with
+ * the k-th member of the left block (node_map of concatenate_alignments) -- a permutation of the right block's members.
+ * Per edge, exactly as the reference (the list order is observable: its Edit compares Vecs):
+ *   X' = X, or with *_rc the consensus reverse-complemented (io/seq.rs:9-33) and every member's edit Edit::reverse_complement(len)
+ *        (edits.rs:257-276): sub pos -> len-pos-1, alt complemented; del pos -> len-pos-len_d; ins pos -> len-pos, letters
+ *        reverse-complemented; each list then STABLY sorted by position
+ *   consensus  left' ++ right'
+ *   member k   e_left'.concat(e_right'.shift(L_left)) (edits.rs:278-304): subs and dels the left list followed by the shifted right list,
+ *        not re-sorted; inss the left list, then every right insertion in order either appended to the FIRST insertion already in the
+ *        accumulated list with the same position (its letters extended) or pushed -- a left insertion at L_left and a right one at 0 become
+ *        one, right insertions that share a position become one, equal positions inside the left list stay separate
+ * Output (freed with pga_merge_free) in the same layout, so that out->blocks, out->members, out->subs / dels / inss and out->ins_seq are
+ * the first arguments of the next pga_merge_blocks call or of pga_reconstruct (n_blocks = n_edges) by pointer arithmetic only: blocks[e]
+ * has its consensus in out->cons (every consensus at a multiple of 16), cons_len = L_left + L_right and the left block's n_members;
+ * members[] edge after edge in the LEFT block's member order (edges[e].member_off is the edge's first), the edits packed in that order.
+ * out->ins_seq holds new letters: every output insertion's seq_off points into it (a member's letters start at a multiple of 16), none
+ * into the caller's buffer.
+ * edges[e].status: 0 built; 2 a block taken with *_rc holds a letter the complement table rejects (the reference's Err) -- in its
+ * consensus, an insertion or a substitution's alt, also one that lies under a deletion.  A status-2 edge keeps its slots: counts and
+ * offsets do not depend on a status; its letters are as built and not to be used.  Other edges are not affected.
+ * Malformed input fails the call before anything is launched (-1, message in pga_last_error()): what fails pga_reconstruct, an edge that
+ * names a block out of range, two blocks of different depth, a partner that is no permutation, L_left + L_right >= 2^30, more than 2^30
+ * inserted letters in one member.  cons_len == 0 and n_members == 0 are legal.  n_edges == 0 returns empty lists without a device call. */
+typedef struct { uint32_t left, right; int32_t left_rc, right_rc; } pga_merge_edge_t;   /* block indices; *_rc: reverse_complement first */
+typedef struct { int32_t status, pad; uint64_t member_off; } pga_merge_res_t;          /* one per edge */
+typedef struct {
+	pga_merge_res_t *edges;
+	pga_rc_block_t  *blocks;     /* one per edge */
+	pga_rc_member_t *members;    /* edge after edge, in the left block's member order */
+	pga_sub_t *subs; pga_del_t *dels; pga_ins_t *inss; char *ins_seq; char *cons;
+} pga_merge_out_t;
+int pga_merge_blocks(int64_t n_blocks, const pga_rc_block_t *blocks, const pga_rc_member_t *members, const pga_sub_t *subs, const pga_del_t *dels,
+                     const pga_ins_t *inss, const char *ins_seq, int64_t n_edges, const pga_merge_edge_t *edges, const uint32_t *partner, pga_merge_out_t *out);
+void pga_merge_free(pga_merge_out_t *out);
 int pga_stats_version(void);    /* == PGA_STATS_VERSION of the header the library was built with */
 /* Measurement only (no reference interface behind it): the kern_ms sums of pga_stats_t count overlapping launches on different streams
  * and batches several times.  Between pga_busy_begin() and pga_busy_end() every event-bracketed launch of the process leaves its interval

@@ -995,6 +995,29 @@ extern "C" int pga_slice_blocks(int64_t n_blocks, const pga_slice_block_t *block
 	} catch (std::exception &e) { pga_slice_free(out); set_err(e.what()); return -1; }
 }
 
+// ---------------------------------------------------------------- simplify's block concatenations (pga_merge.hip)
+namespace pga {
+void merge_blocks_host(int64_t n_blocks, const pga_rc_block_t *blocks, const pga_rc_member_t *members, const pga_sub_t *subs, const pga_del_t *dels, const pga_ins_t *inss,
+                       const char *ins_seq, int64_t n_edges, const pga_merge_edge_t *edges, const uint32_t *partner, pga_merge_out_t *out);
+}
+extern "C" void pga_merge_free(pga_merge_out_t *o)
+{
+	if (!o) return;
+	free(o->edges); free(o->blocks); free(o->members); free(o->subs); free(o->dels); free(o->inss); free(o->ins_seq); free(o->cons);
+	memset(o, 0, sizeof(*o));
+}
+extern "C" int pga_merge_blocks(int64_t n_blocks, const pga_rc_block_t *blocks, const pga_rc_member_t *members, const pga_sub_t *subs, const pga_del_t *dels,
+                                const pga_ins_t *inss, const char *ins_seq, int64_t n_edges, const pga_merge_edge_t *edges, const uint32_t *partner, pga_merge_out_t *out)
+{
+	if (!out) { set_err("pga_merge_blocks: null output"); return -1; }
+	memset(out, 0, sizeof(*out));
+	try {
+		require_device();
+		pga::merge_blocks_host(n_blocks, blocks, members, subs, dels, inss, ins_seq, n_edges, edges, partner, out);
+		return 0;
+	} catch (std::exception &e) { pga_merge_free(out); set_err(e.what()); return -1; }
+}
+
 // ---------------------------------------------------------------- reconstruct / verify (pga_reconstruct.hip)
 namespace pga {
 void reconstruct_host(int64_t n_blocks, const pga_rc_block_t *blocks, const pga_rc_member_t *members, const pga_sub_t *subs, const pga_del_t *dels, const pga_ins_t *inss,
