@@ -215,7 +215,8 @@ void pga_free(void *p);
  * member's substitutions are reconciled, edits.rs:196-238) or edit_consensus_and_realign (kind 2, pangraph_block.rs:295-332: the majority
  * edits applied to the consensus, every member's sequence rebuilt with Edit::apply and re-aligned by map_variations with the band of
  * BandParameters::from_edits).  Counting, Edit::apply, reconciliation and the re-alignment run on the device; sequences built there feed the
- * aligner without leaving it.  detach_unaligned_nodes and the node / path maps (reconsensus.rs:76-88) stay with the caller.
+ * aligner without leaving it.  detach_unaligned_nodes on the realigned blocks (reconsensus.rs:85) is pga_detach_unaligned below, fed from this
+ * entry's output; the node / path maps (reconsensus.rs:76-88) stay with the caller.
  * Input: the members of block b are the next blocks[b].n_members entries of members[] (the reference's BTreeMap order), the edits of a
  * member the next n_subs / n_dels / n_inss entries of subs / dels / inss (insertion letters: ins_seq[seq_off .. seq_off + len)).
  * Output (freed with pga_rc_free): per block its kind, its consensus afterwards and its majority edits; per member (input order) its edits
@@ -469,6 +470,56 @@ typedef struct {
 int pga_merge_blocks(int64_t n_blocks, const pga_rc_block_t *blocks, const pga_rc_member_t *members, const pga_sub_t *subs, const pga_del_t *dels,
                      const pga_ins_t *inss, const char *ins_seq, int64_t n_edges, const pga_merge_edge_t *edges, const uint32_t *partner, pga_merge_out_t *out);
 void pga_merge_free(pga_merge_out_t *out);
+
+/* ---- self-merge: detach_unaligned_nodes (packages/pangraph/src/pangraph/detach_unaligned.rs:24-114) ----
+ * pga_detach_unaligned takes the members without an aligned position out of their blocks and makes each a singleton block of its own
+ * sequence.  The reference runs it on the merged blocks right after solve_promise (graph_merging.rs:154) and on the realigned blocks inside
+ * reconsensus_graph (reconsensus/reconsensus.rs:85): pga_solve_promises -> pga_detach_unaligned -> pga_reconsensus -> pga_detach_unaligned
+ * is that chain in one data layout.  The node map (same node id, new block id, forward strand, position kept) stays with the caller
+ * (pangraph_amd/detach.py), which reads it off orphans[] and member_map[] without a search.
+ * Blocks, members and edits in the layout of pga_reconstruct; who[m] belongs to global member m.  Inputs are only read.
+ *   unaligned      Edit::aligned_count(cons_len) == 0 (edits.rs:439-442): cons_len.saturating_sub(the SUM of the deletion lengths), added
+ *                  in 64 bits -- the plain sum, not the union of the intervals.  The validation admits deletions that overlap (each must
+ *                  lie inside the consensus, nothing else is asked), so two deletions over the same half of a consensus make a member
+ *                  unaligned although half of the consensus is in its sequence; that is the reference's rule and it is kept.  cons_len == 0
+ *                  makes every member of the block unaligned, one without edits included.  Insertions and substitutions play no part.
+ *   blocks[b], b < n_blocks (input)   the input block without its unaligned members: the caller's consensus pointer (nothing is copied),
+ *                  n_members the number kept.  A block left without a member stays, as in the reference.
+ *   members[]      the kept members of block 0, then those of block 1, ... in input order, their three lists packed in that order; a kept
+ *                  insertion keeps its seq_off into the caller's ins_seq (the rule of pga_slice_blocks), the call owns no insertion letters:
+ *                  the next call takes out->blocks, out->members, out->subs, out->dels, out->inss and the caller's own ins_seq.  Behind the
+ *                  kept members one member per singleton block with the counts 0, 0, 0 (PangraphBlock::from_consensus).
+ *   blocks[n_blocks (input) + k]   one per unaligned member in the reference's push order (block after block, inside a block in member
+ *                  order): the letters are Edit::apply of the member's edits to its block's consensus (edits.rs:307-329, list-order rules
+ *                  as in pga_reconstruct), reverse-complemented (io/seq.rs:9-33) when who[m].reverse != 0; consensus points into out->cons
+ *                  (every sequence at a multiple of 16), n_members = 1; an empty sequence gives cons_len = 0.
+ *   orphans[k]     member: the global input member; block: its index in out->blocks; len: the sequence length; node_id: copied from who;
+ *                  block_id: id((node_id, &seq)) of utils/id.rs -- XXH64, seed 0, over node_id as a little-endian u64, the length as a
+ *                  little-endian u64, then the letters (the derived Hash of NodeId(usize), Seq { Vec<AsciiChar> }, AsciiChar(u8) and std's
+ *                  length prefix of a slice); computed on the host from the downloaded letters.
+ *                  status, the first that applies: 0 built; 2 a reverse orphan holds a letter the complement table rejects (the
+ *                  reference's Err); 3 a literal '-' came out (Edit::apply would strip it; as pga_reconstruct).  With a non-zero status
+ *                  block_id is 0 and the letters are as built and not to be used.  Counts and offsets never depend on a status and other
+ *                  orphans are not affected.
+ *   member_map[m]  the index in out->members of input member m, kept or detached.
+ * When no member is unaligned out->cons and out->orphans are NULL, no letter is built, and the output equals the input.
+ * Malformed input fails the call before anything is launched (-1, message in pga_last_error()): what fails pga_reconstruct, a NULL `who`
+ * with members present, NULL insertion letters with a non-zero length, a detached member longer than 2^31 letters.  n_blocks == 0 returns
+ * empty lists without a device call.  Freed with pga_detach_free. */
+typedef struct { uint64_t node_id; int32_t reverse, pad; } pga_detach_member_t;   /* per input member: its NodeId; old node's strand().is_reverse() */
+typedef struct { uint64_t member, node_id, block_id; uint32_t block, len; int32_t status, pad; } pga_detach_orphan_t;
+typedef struct {
+	int64_t n_blocks, n_orphans;               /* n_blocks = input n_blocks + n_orphans */
+	pga_rc_block_t  *blocks;
+	pga_rc_member_t *members;                  /* as many as the input has */
+	pga_sub_t *subs; pga_del_t *dels; pga_ins_t *inss;
+	char *cons;                                /* letters of the new singleton blocks only */
+	int64_t *member_map;
+	pga_detach_orphan_t *orphans;
+} pga_detach_out_t;
+int pga_detach_unaligned(int64_t n_blocks, const pga_rc_block_t *blocks, const pga_rc_member_t *members, const pga_sub_t *subs, const pga_del_t *dels,
+                         const pga_ins_t *inss, const char *ins_seq, const pga_detach_member_t *who, pga_detach_out_t *out);
+void pga_detach_free(pga_detach_out_t *out);
 int pga_stats_version(void);    /* == PGA_STATS_VERSION of the header the library was built with */
 /* Measurement only (no reference interface behind it): the kern_ms sums of pga_stats_t count overlapping launches on different streams
  * and batches several times.  Between pga_busy_begin() and pga_busy_end() every event-bracketed launch of the process leaves its interval

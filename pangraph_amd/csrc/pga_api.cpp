@@ -1018,6 +1018,29 @@ extern "C" int pga_merge_blocks(int64_t n_blocks, const pga_rc_block_t *blocks, 
 	} catch (std::exception &e) { pga_merge_free(out); set_err(e.what()); return -1; }
 }
 
+// ---------------------------------------------------------------- detach_unaligned_nodes (pga_detach.hip)
+namespace pga {
+void detach_unaligned_host(int64_t n_blocks, const pga_rc_block_t *blocks, const pga_rc_member_t *members, const pga_sub_t *subs, const pga_del_t *dels, const pga_ins_t *inss,
+                           const char *ins_seq, const pga_detach_member_t *who, pga_detach_out_t *out);
+}
+extern "C" void pga_detach_free(pga_detach_out_t *o)
+{
+	if (!o) return;
+	free(o->blocks); free(o->members); free(o->subs); free(o->dels); free(o->inss); free(o->cons); free(o->member_map); free(o->orphans);
+	memset(o, 0, sizeof(*o));
+}
+extern "C" int pga_detach_unaligned(int64_t n_blocks, const pga_rc_block_t *blocks, const pga_rc_member_t *members, const pga_sub_t *subs, const pga_del_t *dels,
+                                    const pga_ins_t *inss, const char *ins_seq, const pga_detach_member_t *who, pga_detach_out_t *out)
+{
+	if (!out) { set_err("pga_detach_unaligned: null output"); return -1; }
+	memset(out, 0, sizeof(*out));
+	try {
+		require_device();
+		pga::detach_unaligned_host(n_blocks, blocks, members, subs, dels, inss, ins_seq, who, out);
+		return 0;
+	} catch (std::exception &e) { pga_detach_free(out); set_err(e.what()); return -1; }
+}
+
 // ---------------------------------------------------------------- reconstruct / verify (pga_reconstruct.hip)
 namespace pga {
 void reconstruct_host(int64_t n_blocks, const pga_rc_block_t *blocks, const pga_rc_member_t *members, const pga_sub_t *subs, const pga_del_t *dels, const pga_ins_t *inss,
