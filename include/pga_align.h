@@ -133,6 +133,30 @@ int pga_stage_extd2(int32_t n_jobs, const uint8_t *const *q, const int32_t *qlen
  * the workgroup pipeline gave to the other banded kernels, handed_back[1] = problems a corridor / banded / strip kernel gave to the full-matrix
  * and workgroup kernels (no proof, a maximum outside 16 bits, a dry pool) */
 void pga_stage_dp_routes(int64_t by_class[14], int64_t handed_back[2]);
+/* mg_lchain_rmq (lchain.c:250-368) on anchors given as they are: n_seq queries, query q holding the anchors [q_aoff[q], q_aoff[q+1]) of anchors_xy
+ * (two uint64 per anchor, in the order the reference's function would receive them), chained with the explicit parameters of cp.
+ * mode 0: the reference's procedure as a batch runs it; 1: the same with the counting instantiation of the fast sweep kernel, whose counters
+ * pga_stage_chain_routes hands out; 2: the tie-order-independent route (candidates of equal score in stable order) with need[q] != 0 where
+ * an order event says the query needs the reference's procedure.  PGA_CHAIN_EXACT_ONLY=1 (read per call) sends every segment to the tree kernel.
+ * Caller-allocated outputs: n_u, n_v, ev, need [n_seq]; u, f, p [n_a]; chain_xy [2 n_a].  Query q's chains are u[q_aoff[q] .. +n_u[q]), its
+ * compacted anchors chain_xy[2 q_aoff[q] .. +2 n_v[q]); f[i], p[i]: score and query-local predecessor (-1: none) of EVERY anchor as the
+ * backtrack reads them; ev[q]: the backtrack's order events (bit 0 a walk stopped at a mark of its own score, 1 a candidate marked by a chain
+ * of its own score, 2 two chains start at one target position, 3 two chains from candidates of equal score, 4 bits 2 and 3 where it shows). */
+typedef struct {
+	int32_t max_gap, rmq_inner_dist, bw, max_chain_skip, rmq_size_cap, min_cnt, min_chain_score;
+	float chain_gap_scale, chain_skip_scale;
+	int32_t k;
+} pga_chain_params_t;
+int pga_stage_chain_anchors(int32_t n_seq, const uint64_t *q_aoff, const uint64_t *anchors_xy, const pga_chain_params_t *cp, int mode,
+                            int32_t *n_u, int32_t *n_v, uint64_t *u, uint64_t *chain_xy, int32_t *f, int32_t *p, uint32_t *ev, uint32_t *need);
+/* which branch of the chain sweep answered, summed over the mode-1 calls of pga_stage_chain_anchors since the last call of this function
+ * (process-wide, copied out and zeroed): 0 segments swept by the fast kernel; 1-4 segments it handed to the tree kernel (ring overflow, tree-size
+ * cap, tied minimum, too many inner candidates); 5 anchors taken by the co-linear stretch; 6 by the single-anchor shortcut; 7 inner scans
+ * skipped by the f + span bound; 8 inner scans from registers; 9 in chunked form; 10 inner scans that re-ranked an unsorted window; 11 inner
+ * scans stopped by max_chain_skip; 12 range-min answers taken from a block summary; 13 summary blocks scanned anchor by anchor; 14 window
+ * reloads of the backtrack's walks */
+#define PGA_N_CHAIN_ROUTES 15
+void pga_stage_chain_routes(int64_t out[PGA_N_CHAIN_ROUTES]);
 /* radix_sort_128x (ksort.h:101-151, misc.c:155-159), the exact replay incl. the arrangement of equal keys: sorts every array
  * [seg_off[s], seg_off[s+1]) of the n_seg arrays in xy (two uint64 per record: x = key, y = payload) in place */
 int pga_stage_sort(int32_t n_seg, const uint64_t *seg_off, uint64_t *xy);

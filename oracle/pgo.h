@@ -57,6 +57,9 @@ pg128 *pgo_collect_anchors(const pgo_index_t *ix, const mm_mapopt_t *opt, const 
 /* ---- chaining (pgo_chain.c) ---- */
 pg128 *pgo_lchain_rmq(int max_dist, int max_dist_inner, int bw, int max_chn_skip, int cap_rmq_size, int min_cnt, int min_sc,
                       float chn_pen_gap, float chn_pen_skip, int64_t n, pg128 *a, int *n_u, uint64_t **u);
+/* the same, and f[] / p[] of every anchor (score, predecessor index or -1) as the backtrack receives them: n entries each, caller-allocated */
+pg128 *pgo_lchain_rmq_fp(int max_dist, int max_dist_inner, int bw, int max_chn_skip, int cap_rmq_size, int min_cnt, int min_sc,
+                         float chn_pen_gap, float chn_pen_skip, int64_t n, pg128 *a, int *n_u, uint64_t **u, int32_t *f_out, int64_t *p_out);
 
 /* ---- DP (pgo_ksw.c) ---- */
 typedef struct {

@@ -364,8 +364,9 @@ static int64_t bk_end(int32_t max_drop, const pg128 *z, const int32_t *f, const 
 	return max_i;
 }
 
-pg128 *pgo_lchain_rmq(int max_dist, int max_dist_inner, int bw, int max_chn_skip, int cap_rmq_size, int min_cnt, int min_sc,
-                      float chn_pen_gap, float chn_pen_skip, int64_t n, pg128 *a, int *n_u_, uint64_t **u_)
+/* f_out / p_out (optional, n entries each): f[] and p[] of lchain.c:351 as the backtrack receives them */
+static pg128 *lchain_rmq(int max_dist, int max_dist_inner, int bw, int max_chn_skip, int cap_rmq_size, int min_cnt, int min_sc,
+                         float chn_pen_gap, float chn_pen_skip, int64_t n, pg128 *a, int *n_u_, uint64_t **u_, int32_t *f_out, int64_t *p_out)
 {
 	int32_t *f, *t, *v, max_drop = bw;
 	int64_t *p, i, i0, st = 0, st_inner = 0;
@@ -464,6 +465,8 @@ pg128 *pgo_lchain_rmq(int max_dist, int max_dist_inner, int bw, int max_chn_skip
 		v[i] = max_j >= 0 && v[max_j] > max_f ? v[max_j] : max_f;
 	}
 	free(T.nd); free(T.free_list); free(Ti.nd); free(Ti.free_list); free(slot); free(slot_i);
+	if (f_out) memcpy(f_out, f, (size_t)n * 4);
+	if (p_out) memcpy(p_out, p, (size_t)n * 8);
 
 	/* ---- backtrack (lchain.c:27-76): candidate ends sorted by score with the unstable radix sort ---- */
 	int64_t n_z = 0, k, n_v = 0;
@@ -515,4 +518,16 @@ pg128 *pgo_lchain_rmq(int max_dist, int max_dist_inner, int bw, int max_chn_skip
 	memcpy(u, u2, (size_t)n_u * 8);
 	free(a); free(b); free(wv); free(u2); free(v);
 	return out;
+}
+
+pg128 *pgo_lchain_rmq(int max_dist, int max_dist_inner, int bw, int max_chn_skip, int cap_rmq_size, int min_cnt, int min_sc,
+                      float chn_pen_gap, float chn_pen_skip, int64_t n, pg128 *a, int *n_u_, uint64_t **u_)
+{
+	return lchain_rmq(max_dist, max_dist_inner, bw, max_chn_skip, cap_rmq_size, min_cnt, min_sc, chn_pen_gap, chn_pen_skip, n, a, n_u_, u_, 0, 0);
+}
+
+pg128 *pgo_lchain_rmq_fp(int max_dist, int max_dist_inner, int bw, int max_chn_skip, int cap_rmq_size, int min_cnt, int min_sc,
+                         float chn_pen_gap, float chn_pen_skip, int64_t n, pg128 *a, int *n_u_, uint64_t **u_, int32_t *f_out, int64_t *p_out)
+{
+	return lchain_rmq(max_dist, max_dist_inner, bw, max_chn_skip, cap_rmq_size, min_cnt, min_sc, chn_pen_gap, chn_pen_skip, n, a, n_u_, u_, f_out, p_out);
 }

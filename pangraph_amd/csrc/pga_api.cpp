@@ -817,6 +817,38 @@ extern "C" int pga_stage_extd2(int32_t n_jobs, const uint8_t *const *q, const in
 
 extern "C" void pga_stage_dp_routes(int64_t by_class[14], int64_t handed_back[2]) { dp_routes_take(by_class, handed_back); }
 
+static_assert(pga::CHAIN_N_ROUTES == PGA_N_CHAIN_ROUTES, "pga_stage_chain_routes and the chain sweep number the route counters alike");
+extern "C" int pga_stage_chain_anchors(int32_t n_seq, const uint64_t *q_aoff, const uint64_t *anchors_xy, const pga_chain_params_t *cp, int mode,
+                                       int32_t *n_u, int32_t *n_v, uint64_t *u, uint64_t *chain_xy, int32_t *f, int32_t *p, uint32_t *ev, uint32_t *need)
+{
+	try {
+		require_device();
+		if (n_seq < 0 || !q_aoff || !cp || !n_u || !n_v || !ev || !need) throw std::runtime_error("pga_stage_chain_anchors: null argument");
+		if (mode < 0 || mode > 2) throw std::runtime_error("pga_stage_chain_anchors: mode is 0 (the reference's procedure), 1 (the same, counted) or 2 (tie-order-independent)");
+		std::vector<uint64_t> off(q_aoff, q_aoff + n_seq + 1);
+		if (off[0] != 0) throw std::runtime_error("pga_stage_chain_anchors: q_aoff[0] != 0");
+		for (int q = 0; q < n_seq; ++q) if (off[(size_t)q + 1] < off[(size_t)q]) throw std::runtime_error("pga_stage_chain_anchors: q_aoff descends");
+		const size_t n_a = (size_t)off[(size_t)n_seq];
+		if (n_a && (!anchors_xy || !u || !chain_xy || !f || !p)) throw std::runtime_error("pga_stage_chain_anchors: null argument");
+		std::vector<u128> a(n_a);
+		for (size_t i = 0; i < n_a; ++i) a[i].x = anchors_xy[2 * i], a[i].y = anchors_xy[2 * i + 1];
+		mm_mapopt_t mo; memset(&mo, 0, sizeof(mo));
+		mo.max_gap = cp->max_gap, mo.rmq_inner_dist = cp->rmq_inner_dist, mo.bw = cp->bw, mo.max_chain_skip = cp->max_chain_skip, mo.rmq_size_cap = cp->rmq_size_cap;
+		mo.min_cnt = cp->min_cnt, mo.min_chain_score = cp->min_chain_score, mo.chain_gap_scale = cp->chain_gap_scale, mo.chain_skip_scale = cp->chain_skip_scale;
+		ChainResult CR; ChainTap T; T.count = mode == 1;
+		chain_anchors_tap(a, off, mo, cp->k, mode == 2, CR, T, 0);
+		for (int q = 0; q < n_seq; ++q) { n_u[q] = CR.n_u[(size_t)q]; n_v[q] = CR.n_v[(size_t)q]; ev[q] = T.ev[(size_t)q]; need[q] = T.need[(size_t)q]; }
+		for (size_t i = 0; i < n_a; ++i) {
+			u[i] = i < CR.u.size() ? CR.u[i] : 0;
+			chain_xy[2 * i] = i < CR.a.size() ? CR.a[i].x : 0, chain_xy[2 * i + 1] = i < CR.a.size() ? CR.a[i].y : 0;
+			f[i] = T.f[i], p[i] = T.p[i];
+		}
+		return 0;
+	} catch (std::exception &e) { set_err(e.what()); return -1; }
+}
+
+extern "C" void pga_stage_chain_routes(int64_t out[PGA_N_CHAIN_ROUTES]) { chain_routes_take(out); }
+
 // ---------------------------------------------------------------- split_matches + filter_matches on the device (pga_filter.hip)
 namespace pga {
 struct FilterParams { int32_t thr, flags; double alpha, beta; };

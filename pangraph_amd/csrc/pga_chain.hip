@@ -263,9 +263,10 @@ __device__ __forceinline__ double cf_pri(int32_t f, int32_t x, int32_t y, float 
 // is in flight while the current one is swept) and f/p leave through the rings once per block, so the per-anchor
 // critical path touches LDS only.  Inside the sweep the wave is its own synchronisation domain (wavefront-scope
 // fences: LDS operations of one wave execute in order).
-// (the phase clocks of the profile cost ~600 clocks per anchor: they only exist in the PROF instantiation)
-#define CF_CLK() (PROF ? (long long)clock64() : 0LL)
-template <int CF_W, bool PROF>
+// PROF: 0 the production kernel; 1 the route counters of pga_stage_chain_routes (which branch answered how often: tests); 2 the counters and the phase
+// clocks of the profile (~600 clocks per anchor).  Nothing of either exists in instantiation 0.
+#define CF_CLK() (PROF == 2 ? (long long)clock64() : 0LL)
+template <int CF_W, int PROF>
 __global__ __launch_bounds__(64)
 void k_chain_fast(const u128 *__restrict__ a, const uint64_t *__restrict__ seg_start, const uint32_t *__restrict__ seg_order, uint32_t n_seg,
                   uint64_t n_total, const uint64_t *__restrict__ q_aoff, int n_seq, ChainParams P,
@@ -312,6 +313,7 @@ void k_chain_fast(const u128 *__restrict__ a, const uint64_t *__restrict__ seg_s
 	const bool shortcut_ok = P.cap >= CF_W;                  // (the tree-size cap of lchain.c:304 cannot bind inside the ring)
 	const unsigned long long c0 = wall_clock64();
 	unsigned long long n_scan = 0, n_inner = 0, n_incand = 0, n_slow = 0, n_pev = 0, n_py = 0;
+	unsigned long long n_stretch = 0, n_chunk = 0, n_skipstop = 0, n_sum = 0, n_sumscan = 0;   // (PROF only) of n_py: by the stretch; of n_inner: chunked
 	long long tk_scan = 0, tk_red = 0, tk_best = 0, tk_inner = 0, tk_store = 0;
 	u128 nxtv; nxtv.x = 0, nxtv.y = 0;
 	if (lane < n) nxtv = A[lane];
@@ -367,7 +369,7 @@ void k_chain_fast(const u128 *__restrict__ a, const uint64_t *__restrict__ seg_s
 						fs_floor = max(max(fs_floor, fs_last), fsm);
 						fs_last = __builtin_amdgcn_readlane(bf, lb) + __builtin_amdgcn_readlane(bsp, lb);
 					}
-					if (PROF) n_py += R;
+					if (PROF) { n_py += R; n_stretch += R; }
 					i0 = i + R - 1;
 					i += R - 1;
 					continue;
@@ -412,15 +414,16 @@ void k_chain_fast(const u128 *__restrict__ a, const uint64_t *__restrict__ seg_s
 				//     wholly inside the window and the y range contributes its minimum, one wholly outside the y range nothing,
 				//     the others are scanned anchor by anchor
 				const int32_t S = blk < (i0 & ~63) ? blk : (i0 & ~63);
-				bool part = false;
+				bool part = false, took = false;
 				if (lane < CF_W / 64 && sm_blk >= 0 && sm_blk + 64 > st && sm_blk + 64 <= S) {
 					const bool none = sm_ymax <= y_lo || sm_ymin > yi || (sm_ymin == yi && !(seg_is_query_start && sm_blk == 0));
 					// wholly inside the window -- or partly evicted, but the block's unique minimum is still inside: then it is also
 					// the (unique) minimum of the surviving part
-					if ((sm_blk >= st || sm_arg >= st) && sm_ymin > y_lo && sm_ymax < yi) { best = sm_pri; best_j = sm_arg < 0 ? sm_blk : sm_arg; tie = sm_arg < 0; }
+					if ((sm_blk >= st || sm_arg >= st) && sm_ymin > y_lo && sm_ymax < yi) { best = sm_pri; best_j = sm_arg < 0 ? sm_blk : sm_arg; tie = sm_arg < 0; took = true; }
 					else if (!none) part = true;
 				}
 				unsigned long long pm = __ballot(part);
+				if (PROF) { n_sum += __popcll(__ballot(took)); n_sumscan += __popcll(pm); }
 				while (pm) {
 					const int bsel = __ffsll((long long)pm) - 1;
 					pm &= pm - 1;
@@ -490,7 +493,7 @@ void k_chain_fast(const u128 *__restrict__ a, const uint64_t *__restrict__ seg_s
 					if (n_in > CF_WI) { bail = true; why = 4; break; }
 					if (n_in > CF_MAXIN) {
 						// ---- crowded inner window (repeats): the same scan, 64 candidates at a time from LDS ----
-						++n_inner; n_incand += n_in;
+						++n_inner; n_incand += n_in; if (PROF) ++n_chunk;
 						auto cand = [&](int32_t jc, int32_t &sc, bool &ok) -> bool {    // candidate jc: inside the y range? its score, inside the band?
 							const CfEnt ec = r_e[jc & CF_M];
 							if (!(ec.y <= yi - 1 && ec.y >= yi - max_dist_inner)) { sc = 0; ok = false; return false; }
@@ -555,7 +558,7 @@ void k_chain_fast(const u128 *__restrict__ a, const uint64_t *__restrict__ seg_s
 								const int c = rest ? __ffsll((long long)rest) - 1 : 64;
 								const unsigned long long range = (c >= 64 ? ~0ULL : ((1ULL << c) - 1)) & ~((1ULL << pos) - 1);
 								n_skip += __popcll(inc & range);
-								if (n_skip > P.max_skip) { stop = true; break; }
+								if (n_skip > P.max_skip) { stop = true; if (PROF) ++n_skipstop; break; }
 								if (c >= 64) break;
 								rest &= rest - 1;
 								last = c; if (n_skip > 0) --n_skip;
@@ -637,7 +640,7 @@ void k_chain_fast(const u128 *__restrict__ a, const uint64_t *__restrict__ seg_s
 							const int c = rest ? __ffsll((long long)rest) - 1 : 64;
 							const unsigned long long range = (c >= 64 ? ~0ULL : ((1ULL << c) - 1)) & ~((1ULL << pos) - 1);
 							n_skip += __popcll(inc & range);
-							if (n_skip > P.max_skip) { stop = true; break; }
+							if (n_skip > P.max_skip) { stop = true; if (PROF) ++n_skipstop; break; }
 							if (c >= 64) break;
 							rest &= rest - 1;
 							last = c; if (n_skip > 0) --n_skip;
@@ -681,6 +684,7 @@ void k_chain_fast(const u128 *__restrict__ a, const uint64_t *__restrict__ seg_s
 		const unsigned long long dt = wall_clock64() - c0;
 		atomicAdd(&prof[0], dt); atomicMax(&prof[1], dt); atomicMax(&prof[2], (unsigned long long)n);
 		atomicAdd(&prof[12], n_pev); atomicAdd(&prof[13], n_py);
+		atomicAdd(&prof[16], n_stretch); atomicAdd(&prof[17], n_chunk); atomicAdd(&prof[18], n_skipstop); atomicAdd(&prof[19], n_sum); atomicAdd(&prof[20], n_sumscan);
 		atomicAdd(&prof[3], n_scan); atomicAdd(&prof[4], n_inner); atomicAdd(&prof[5], n_incand); atomicAdd(&prof[6], n_slow);
 		atomicAdd(&prof[7], (unsigned long long)tk_scan); atomicAdd(&prof[8], (unsigned long long)tk_red); atomicAdd(&prof[9], (unsigned long long)tk_best); atomicAdd(&prof[10], (unsigned long long)tk_inner); atomicAdd(&prof[11], (unsigned long long)tk_store);
 	}
@@ -1012,6 +1016,7 @@ void k_bt_walk(int n_seq, const uint64_t *__restrict__ q_aoff, const u128 *__res
 	if (prof && lane == 0) {
 		const unsigned long long c3 = wall_clock64();
 		atomicAdd(&prof[0], c1 - c0); atomicAdd(&prof[1], c2 - c1); atomicAdd(&prof[2], c3 - c2);
+		atomicAdd(&prof[13], pc_reload);                                  // (of all queries: pga_stage_chain_routes)
 		atomicMax(&prof[3], c1 - c0); atomicMax(&prof[4], c2 - c1); atomicMax(&prof[5], c3 - c2);
 		// of the query with the most anchors: walks, window reloads, walk iterations, candidate trips, ticks inside walks, ticks setting marks
 		if ((unsigned long long)n >= atomicMax(&prof[6], (unsigned long long)n)) { prof[7] = pc_walks; prof[8] = pc_reload; prof[9] = pc_iter; prof[10] = pc_trips; prof[11] = pc_walktk; prof[12] = pc_marktk; }
@@ -1110,15 +1115,27 @@ __global__ void k_gather_queries(int n_sub, const uint64_t *__restrict__ src_off
 	for (uint64_t i = (uint64_t)blockIdx.y * blockDim.x + threadIdx.x; i < n; i += (uint64_t)gridDim.y * blockDim.x) out[d + i] = a[s + i];
 }
 
+// Route counters of the stage tap pga_stage_chain_routes (tests): which branch of the sweep answered how often, summed over the calls of
+// pga_stage_chain_anchors in its counting mode since the last read.  Process-wide; a batch never touches them.
+static std::mutex g_chain_routes_mu;
+static int64_t g_chain_routes[CHAIN_N_ROUTES];
+void chain_routes_take(int64_t out[CHAIN_N_ROUTES])
+{
+	std::lock_guard<std::mutex> lk(g_chain_routes_mu);
+	for (int i = 0; i < CHAIN_N_ROUTES; ++i) { out[i] = g_chain_routes[i]; g_chain_routes[i] = 0; }
+}
+
 // One pass of the stage over the anchors a[0..n_a) of n_seq queries.
 //   spec == false  the reference's procedure: the candidate ends of every query go through the replay of the unstable sort (lchain.c:52) where they hold
 //                  equal scores; `a` must be in the reference's order.
 //   spec == true   `a` may hold equal keys in stable order and the candidates are taken in STABLE order of their scores.  That is the reference's result
 //                  whenever no ORDER EVENT shows (k_bt_walk) -- proof in chain_all -- and need_out[q] says for which queries one did.
 static void chain_core(const DBuf<u128> &a, const DBuf<uint64_t> &q_aoff, const int n_seq, uint64_t n_a, const mm_mapopt_t &opt, int k, ChainResult &O, hipStream_t st, Timers *tm,
-                       bool spec, const uint32_t *d_q_tie_x, std::vector<uint32_t> *need_out)
+                       bool spec, const uint32_t *d_q_tie_x, std::vector<uint32_t> *need_out, ChainTap *tap = nullptr)
 {
 	if (need_out) need_out->assign((size_t)n_seq, 0u);
+	if (tap) { tap->f.clear(); tap->p.clear(); tap->ev.assign((size_t)n_seq, 0u); }
+	const bool counting = tap && tap->count;                 // the counting instantiation of the fast kernel, its counters to g_chain_routes
 	O.n_u.assign((size_t)n_seq, 0); O.n_v.assign((size_t)n_seq, 0); O.u.clear(); O.a.clear(); O.d_a.release();
 	if (n_a == 0) return;
 	if (n_a >= (1ULL << 31)) throw std::runtime_error("pga: more than 2^31 anchors in one batch");
@@ -1189,10 +1206,11 @@ static void chain_core(const DBuf<u128> &a, const DBuf<uint64_t> &q_aoff, const 
 		if (!use_fast && n_seq > 0) PGA_HIP(hipMemsetD32Async((hipDeviceptr_t)seg_q.p, 1, (size_t)n_seq, st));
 		const bool verbose = getenv("PGA_VERBOSE") != nullptr;
 		const bool prof_on = verbose && getenv("PGA_CHAIN_PROF");
-		DBuf<unsigned long long> cprof(16); if (prof_on) cprof.zero(st);
-		if (use_fast && prof_on) hipLaunchKernelGGL((k_chain_fast<2048, true>), dim3(n_seg), dim3(64), 0, st, a.p, seg_start.p, ord.p, n_seg, n_a, q_aoff.p, n_seq, P, f.p, pp.p, seg_flag.p, (const uint32_t*)nullptr, cprof.p);
+		DBuf<unsigned long long> cprof(32); if (prof_on || counting) cprof.zero(st);
+		if (use_fast && prof_on) hipLaunchKernelGGL((k_chain_fast<2048, 2>), dim3(n_seg), dim3(64), 0, st, a.p, seg_start.p, ord.p, n_seg, n_a, q_aoff.p, n_seq, P, f.p, pp.p, seg_flag.p, (const uint32_t*)nullptr, cprof.p);
+		else if (use_fast && counting) hipLaunchKernelGGL((k_chain_fast<2048, 1>), dim3(n_seg), dim3(64), 0, st, a.p, seg_start.p, ord.p, n_seg, n_a, q_aoff.p, n_seq, P, f.p, pp.p, seg_flag.p, (const uint32_t*)nullptr, cprof.p);
 		else if (use_fast) {
-			hipLaunchKernelGGL((k_chain_fast<2048, false>), dim3(n_seg), dim3(64), 0, st, a.p, seg_start.p, ord.p, n_seg, n_a, q_aoff.p, n_seq, P, f.p, pp.p, seg_flag.p, (const uint32_t*)nullptr, (unsigned long long*)nullptr);
+			hipLaunchKernelGGL((k_chain_fast<2048, 0>), dim3(n_seg), dim3(64), 0, st, a.p, seg_start.p, ord.p, n_seg, n_a, q_aoff.p, n_seq, P, f.p, pp.p, seg_flag.p, (const uint32_t*)nullptr, (unsigned long long*)nullptr);
 		}
 		const double ms_fast = verbose ? et.stop() : 0.0;
 		// segments the fast kernel gave up on (rare: ring overflow, a tied minimum, a crowded inner window) are re-run by the tree kernel
@@ -1226,8 +1244,19 @@ static void chain_core(const DBuf<u128> &a, const DBuf<uint64_t> &q_aoff, const 
 			if (prof_on) fprintf(stderr, "[pga]   chain fast clocks/anchor: scan %.0f reduce %.0f best %.0f inner %.0f store %.0f; inner scans skipped by the f + span bound %.3f/anchor; shortcut taken %.3f\n", (double)pr[7] / n_a, (double)pr[8] / n_a, (double)pr[9] / n_a, (double)pr[10] / n_a, (double)pr[11] / n_a, (double)pr[12] / n_a, (double)pr[13] / n_a);
 		}
 		if (tm) { tm->kern[K_CHAIN].ms += ms; tm->kern[K_CHAIN].launches += 1; tm->kern[K_CHAIN].alg_bytes += 36.0 * (double)n_a; } // 16 B anchor read + f,p,v,t
+		if (counting && use_fast) {
+			const std::vector<uint32_t> fl = seg_flag.download(st);
+			const std::vector<unsigned long long> pr = cprof.download(st);
+			std::lock_guard<std::mutex> lk(g_chain_routes_mu);
+			int64_t *R = g_chain_routes;
+			for (uint32_t v : fl) ++R[v == 0 ? CR_FAST : CR_WHY1 + (int)((v < 5 ? v : 1) - 1)];
+			R[CR_STRETCH] += (int64_t)pr[16]; R[CR_SINGLE] += (int64_t)(pr[13] - pr[16]); R[CR_BOUND] += (int64_t)pr[12];
+			R[CR_INNER_REG] += (int64_t)(pr[4] - pr[17]); R[CR_INNER_CHUNK] += (int64_t)pr[17]; R[CR_RERANK] += (int64_t)pr[6]; R[CR_SKIP_STOP] += (int64_t)pr[18];
+			R[CR_SUMMARY] += (int64_t)pr[19]; R[CR_SUMMARY_SCAN] += (int64_t)pr[20];
+		}
 	}
 	hipLaunchKernelGGL(k_fix_pred, dim3(nba), dim3(256), 0, st, seg_start.p, n_seg, n_a, q_aoff.p, n_seq, seg_incl.p, pp.p);
+	if (tap) { tap->f = f.download(st); tap->p = pp.download(st); }       // (before the backtrack: it reads both, writes neither)
 	mark("chain kernels");
 	// backtrack + compact, one lane per query
 	DBuf<u128> z(n_a), w(n_a), out(n_a);
@@ -1236,7 +1265,7 @@ static void chain_core(const DBuf<u128> &a, const DBuf<uint64_t> &q_aoff, const 
 	{
 		EventTimer et(st);
 		const bool verbose = getenv("PGA_VERBOSE") != nullptr;
-		DBuf<unsigned long long> prof(16); if (verbose) prof.zero(st);
+		DBuf<unsigned long long> prof(16); if (verbose || counting) prof.zero(st);
 		DBuf<int64_t> n_z((size_t)n_seq);
 		DBuf<uint32_t> ev((size_t)n_seq), q_tie_f;
 		hipLaunchKernelGGL(k_bt_list, dim3((unsigned)n_seq), dim3(64), 0, st, n_seq, q_aoff.p, f.p, t.p, z.p, P, n_z.p, n_u.p, n_v.p);
@@ -1278,7 +1307,7 @@ static void chain_core(const DBuf<u128> &a, const DBuf<uint64_t> &q_aoff, const 
 		et2.mark();
 		EventTimer et3(st);
 		hipLaunchKernelGGL(k_bt_walk, dim3((unsigned)n_seq), dim3(64), 0, st, n_seq, q_aoff.p, a.p, f.p, pp.p, t.p, v.p, z.p, n_z.p, u.p, w.p, u2.p, out.p, P, n_u.p, n_v.p,
-		                   verbose ? prof.p : (unsigned long long*)nullptr, ev.p);
+		                   verbose || counting ? prof.p : (unsigned long long*)nullptr, ev.p);
 		if (n_a) hipLaunchKernelGGL(k_bt_copy, dim3((unsigned)((n_a + 255) / 256)), dim3(256), 0, st, n_seq, q_aoff.p, (uint64_t)n_a, a.p, v.p, u.p, w.p, n_u.p, n_v.p, out.p);
 		const double ms_walk = et3.stop(K_BACKTRACK);
 		ms_list = et.finish(K_BACKTRACK); ms_sort = et2.finish();
@@ -1287,6 +1316,8 @@ static void chain_core(const DBuf<u128> &a, const DBuf<uint64_t> &q_aoff, const 
 			size_t c[4] = {0, 0, 0, 0}, ft = 0; for (size_t i = 0; i < he.size(); ++i) { c[0] += he[i] & 1; c[1] += (he[i] >> 1) & 1; c[2] += (he[i] >> 2) & 1; c[3] += he[i] != 0; ft += i < hq.size() && hq[i]; }
 			fprintf(stderr, "[pga]   backtrack order events: %zu of %d queries (%zu with equal scores): walk stopped at an equal-score mark %zu, candidate marked by an equal score %zu, equal chain starts %zu\n", c[3], n_seq, ft, c[0], c[1], c[2]);
 		}
+		if (tap) tap->ev = ev.download(st);
+		if (counting) { const std::vector<unsigned long long> pr = prof.download(st); std::lock_guard<std::mutex> lk(g_chain_routes_mu); g_chain_routes[CR_BT_RELOAD] += (int64_t)pr[13]; }
 		if (spec && need_out) {
 			DBuf<uint32_t> need((size_t)n_seq);
 			hipLaunchKernelGGL(k_need_exact, dim3((unsigned)((n_seq + 255) / 256)), dim3(256), 0, st, n_seq, d_q_tie_x, q_tie_f.p, ev.p, seg_q.p, need.p);
@@ -1326,6 +1357,18 @@ static void chain_core(const DBuf<u128> &a, const DBuf<uint64_t> &q_aoff, const 
 	O.d_a = std::move(out);
 	mark("anchors to host");
 	if (vmarks) fprintf(stderr, "[pga]   chain stage, host ms:%s\n", marks.c_str());
+}
+
+// The anchor-level tap (pga_stage_chain_anchors): chain_core on anchors given as they are -- geometry chosen by a test, not produced by seeding.
+// spec: the tie-order-independent route without equal-key knowledge (d_q_tie_x == nullptr), T.need says which queries raised an order event.
+void chain_anchors_tap(const std::vector<u128> &a, const std::vector<uint64_t> &q_aoff, const mm_mapopt_t &opt, int k, bool spec, ChainResult &O, ChainTap &T, hipStream_t st)
+{
+	const int n_seq = (int)q_aoff.size() - 1;
+	DBuf<u128> d_a; d_a.upload(a, st);
+	DBuf<uint64_t> d_off; d_off.upload(q_aoff, st);
+	T.need.assign((size_t)n_seq, 0u);
+	chain_core(d_a, d_off, n_seq, (uint64_t)a.size(), opt, k, O, st, nullptr, spec, nullptr, spec ? &T.need : nullptr, &T);
+	PGA_HIP(sync_stream(st));
 }
 
 // The stage.  minimap2 sorts twice with an UNSTABLE in-place radix sort whose arrangement of equal keys is the outcome of its sequential walk

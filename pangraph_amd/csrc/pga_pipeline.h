@@ -46,6 +46,16 @@ void seed_exact_order(SeedResult &O, const uint32_t *d_need, int n_seq, hipStrea
 // exact_order = false: SR may hold tied queries in stable order (SR.exact == false); queries whose chains could depend on the reference's tie
 // order are detected, re-sorted exactly (seed_exact_order) and chained again
 void chain_all(const SeqSet &S, SeedResult &SR, const mm_mapopt_t &opt, int k, ChainResult &O, hipStream_t st, Timers *tm = nullptr, bool exact_order = true);
+// What the anchor-level tap asks of the chaining pass besides the chains (tests only; a batch passes no tap and nothing changes for it).
+struct ChainTap {
+	bool count = false;              // in: run the counting instantiation of the fast kernel and add its counters to the route counters
+	std::vector<int32_t> f, p;       // out: per anchor, the score and the query-local predecessor (-1 none) as the backtrack reads them
+	std::vector<uint32_t> ev, need;  // out: per query, the order-event word of the backtrack; in the tie-order-independent route, whether the query needs the reference's order
+};
+// route counters of the chain sweep (pga_stage_chain_routes), in this order
+enum { CR_FAST = 0, CR_WHY1, CR_WHY2, CR_WHY3, CR_WHY4, CR_STRETCH, CR_SINGLE, CR_BOUND, CR_INNER_REG, CR_INNER_CHUNK, CR_RERANK, CR_SKIP_STOP, CR_SUMMARY, CR_SUMMARY_SCAN, CR_BT_RELOAD, CHAIN_N_ROUTES };
+void chain_anchors_tap(const std::vector<u128> &a, const std::vector<uint64_t> &q_aoff, const mm_mapopt_t &opt, int k, bool spec, ChainResult &O, ChainTap &T, hipStream_t st);
+void chain_routes_take(int64_t out[CHAIN_N_ROUTES]);   // the counters since the last call, zeroed
 bool exact_sorts_forced();   // PGA_EXACT_SORTS=1: every unstable sort is replayed whether or not the result needs it (round-3 behaviour; the stage taps)
 void align_batch(const SeqSet &S, const mm_mapopt_t &opt, int k, const std::vector<uint64_t> &q_aoff, ChainResult &C, const std::vector<int32_t> &rep_len,
                  std::vector<std::vector<Reg>> &out, int n_threads, Timers *tm, hipStream_t st);

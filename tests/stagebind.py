@@ -306,3 +306,132 @@ def product_chain(dll, seqs, names, sensitivity=10, kmer_length=0, indel_len_thr
     for ptr in (axy, aoff, nu, nv, u, cxy, rep):
         dll.pga_free(ptr)
     return out, mid.value
+
+
+# ---------------------------------------------------------------- chaining on explicit anchors (tests/chain_cases.py)
+class pga_chain_params_t(C.Structure):  # include/pga_align.h
+    _fields_ = [("max_gap", C.c_int32), ("rmq_inner_dist", C.c_int32), ("bw", C.c_int32), ("max_chain_skip", C.c_int32), ("rmq_size_cap", C.c_int32),
+                ("min_cnt", C.c_int32), ("min_chain_score", C.c_int32), ("chain_gap_scale", C.c_float), ("chain_skip_scale", C.c_float), ("k", C.c_int32)]
+
+
+N_CHAIN_ROUTES = 15
+CHAIN_ROUTES = ("fast", "why1_ring", "why2_cap", "why3_tie", "why4_inner", "stretch", "single", "bound", "inner_reg", "inner_chunk", "rerank", "skip_stop",
+                "summary", "summary_scan", "bt_reload")
+
+
+def _chain_np(call, anchors: np.ndarray, prm, want_fp=False):
+    """one query through a chaining function of the reference's signature; anchors: (n, 2) uint64.  -> u (uint64 array), chain ((n_v, 2) uint64)
+    [, f (int32), p (int64)].  The array travels through numpy buffers; the callee frees its input (malloc()ed here)"""
+    a = np.ascontiguousarray(anchors, dtype=np.uint64)
+    n = len(a)
+    f, p = np.zeros(n, np.int32), np.zeros(n, np.int64)
+    none = (np.zeros(0, np.uint64), np.zeros((0, 2), np.uint64))
+    if n == 0:
+        return none + ((f, p) if want_fp else ())
+    _libc.malloc.restype = C.c_void_p
+    _libc.malloc.argtypes = [C.c_size_t]
+    buf = _libc.malloc(n * 16)
+    C.memmove(buf, a.ctypes.data, n * 16)
+    n_u = C.c_int(0)
+    u = C.POINTER(C.c_uint64)()
+    pen_gap = float(np.float32(np.float64(np.float32(prm.chain_gap_scale)) * 0.01 * prm.k))
+    pen_skip = float(np.float32(np.float64(np.float32(prm.chain_skip_scale)) * 0.01 * prm.k))
+    res = call(prm, pen_gap, pen_skip, n, buf, C.byref(n_u), C.byref(u), f, p)
+    us = np.ctypeslib.as_array(u, shape=(n_u.value,)).copy() if n_u.value else none[0]
+    n_v = int((us & np.uint64(0xffffffff)).sum())
+    ch = np.ctypeslib.as_array(C.cast(res, C.POINTER(C.c_uint64)), shape=(n_v, 2)).copy() if res and n_v else none[1]
+    if res:
+        _libc.free(res)
+    if u:
+        _libc.free(u)
+    return (us, ch) + ((f, p) if want_fp else ())
+
+
+_CHAIN_ARGS = [C.c_int] * 7 + [C.c_float, C.c_float, C.c_int64, C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.POINTER(C.c_uint64))]
+
+
+def _chain_ints(prm):
+    return (prm.max_gap, prm.rmq_inner_dist, prm.bw, prm.max_chain_skip, prm.rmq_size_cap, prm.min_cnt, prm.min_chain_score)
+
+
+def ref_chain_np(dll, anchors, prm):
+    """mg_lchain_rmq of the compiled reference on one query with explicit parameters (chain_cases.Params)"""
+    dll.mg_lchain_rmq.restype = C.c_void_p
+    dll.mg_lchain_rmq.argtypes = _CHAIN_ARGS + [C.c_void_p]
+    return _chain_np(lambda o, pg, ps, n, buf, n_u, u, f, p: dll.mg_lchain_rmq(*_chain_ints(o), pg, ps, n, buf, n_u, u, None), anchors, prm)
+
+
+def oracle_chain_np(dll, anchors, prm):
+    dll.pgo_lchain_rmq.restype = C.c_void_p
+    dll.pgo_lchain_rmq.argtypes = _CHAIN_ARGS
+    return _chain_np(lambda o, pg, ps, n, buf, n_u, u, f, p: dll.pgo_lchain_rmq(*_chain_ints(o), pg, ps, n, buf, n_u, u), anchors, prm)
+
+
+def oracle_chain_fp(dll, anchors, prm):
+    """pgo_lchain_rmq_fp: u, chain, f[], p[] (p: predecessor index in the query, -1 none)"""
+    dll.pgo_lchain_rmq_fp.restype = C.c_void_p
+    dll.pgo_lchain_rmq_fp.argtypes = _CHAIN_ARGS + [C.c_void_p, C.c_void_p]
+    return _chain_np(lambda o, pg, ps, n, buf, n_u, u, f, p: dll.pgo_lchain_rmq_fp(*_chain_ints(o), pg, ps, n, buf, n_u, u, f.ctypes.data, p.ctypes.data), anchors, prm, want_fp=True)
+
+
+def oracle_tie_count(dll, anchors, prm):
+    """range-min queries of the restatement's sweep over one query that met a tied minimum (its brute-force debug count)"""
+    chk, n_tie = C.c_int.in_dll(dll, "pgo_dbg_tie_check"), C.c_long.in_dll(dll, "pgo_dbg_n_tie")
+    chk.value, n_tie.value = 1, 0
+    try:
+        oracle_chain_np(dll, anchors, prm)
+    finally:
+        chk.value = 0
+    return int(n_tie.value)
+
+
+def product_chain_anchors(dll, queries, prm, mode):
+    """pga_stage_chain_anchors on a list of queries ((n, 2) uint64 each).  mode 0: the reference's procedure as a batch runs it, 1: the same with the
+    counting fast kernel, 2: the tie-order-independent route.  -> per query dict(u, chain, f, p, ev, need), all numpy"""
+    n_seq = len(queries)
+    off = np.zeros(n_seq + 1, np.uint64)
+    off[1:] = np.cumsum([len(q) for q in queries])
+    n_a = int(off[-1])
+    a = np.ascontiguousarray(np.concatenate([np.asarray(q, np.uint64).reshape(-1, 2) for q in queries], axis=0)) if n_seq else np.zeros((0, 2), np.uint64)
+    cp = pga_chain_params_t(prm.max_gap, prm.rmq_inner_dist, prm.bw, prm.max_chain_skip, prm.rmq_size_cap, prm.min_cnt, prm.min_chain_score,
+                            prm.chain_gap_scale, prm.chain_skip_scale, prm.k)
+    n_u, n_v = np.zeros(n_seq, np.int32), np.zeros(n_seq, np.int32)
+    ev, need = np.zeros(n_seq, np.uint32), np.zeros(n_seq, np.uint32)
+    u, cxy = np.zeros(max(n_a, 1), np.uint64), np.zeros((max(n_a, 1), 2), np.uint64)
+    f, p = np.zeros(max(n_a, 1), np.int32), np.zeros(max(n_a, 1), np.int32)
+    dll.pga_stage_chain_anchors.restype = C.c_int
+    dll.pga_stage_chain_anchors.argtypes = [C.c_int32, C.c_void_p, C.c_void_p, C.POINTER(pga_chain_params_t), C.c_int] + [C.c_void_p] * 8
+    rc = dll.pga_stage_chain_anchors(n_seq, off.ctypes.data, a.ctypes.data, C.byref(cp), mode, n_u.ctypes.data, n_v.ctypes.data, u.ctypes.data, cxy.ctypes.data,
+                                     f.ctypes.data, p.ctypes.data, ev.ctypes.data, need.ctypes.data)
+    if rc != 0:
+        dll.pga_last_error.restype = C.c_char_p
+        raise RuntimeError(dll.pga_last_error().decode())
+    out = []
+    for q in range(n_seq):
+        b, e = int(off[q]), int(off[q + 1])
+        out.append(dict(u=u[b:b + n_u[q]].copy(), chain=cxy[b:b + n_v[q]].copy(), f=f[b:e].copy(), p=p[b:e].copy(), ev=int(ev[q]), need=int(need[q])))
+    return out
+
+
+def product_chain_routes(dll):
+    """pga_stage_chain_routes: the route counters of the mode-1 calls since the last read, by name; the read zeroes them"""
+    out = (C.c_int64 * N_CHAIN_ROUTES)()
+    dll.pga_stage_chain_routes.restype = None
+    dll.pga_stage_chain_routes(out)
+    return dict(zip(CHAIN_ROUTES, list(out)))
+
+
+_CHAIN_EXPECTED = {}
+
+
+def chain_expected(case, ref_dll, oracle_dll):
+    """what a case of tests/chain_cases.py must give, computed once per process and shared (treat as read-only): per query dict(u, chain) of the
+    compiled reference -- the authority for the chains -- and (u, chain, f, p) of the restatement -- the authority for f / p"""
+    if case.name not in _CHAIN_EXPECTED:
+        out = []
+        for q in case.queries:
+            u, ch = ref_chain_np(ref_dll, q, case.params)
+            ou, och, f, p = oracle_chain_fp(oracle_dll, q, case.params)
+            out.append(dict(u=u, chain=ch, o_u=ou, o_chain=och, f=f, p=p))
+        _CHAIN_EXPECTED[case.name] = out
+    return _CHAIN_EXPECTED[case.name]
