@@ -316,8 +316,9 @@ int pga_stage_promise_jobs(int64_t n_promises, const pga_promise_t *promises, co
  * interval computed (interval_node_coords, slice.rs:103-127), from those the new node's position on its path and its strand
  * (new_position_circular / _non_circular, new_strandedness, slice.rs:55-101), and the member left out of the slice when its alignment has
  * become empty (Edit::is_empty_alignment, edits.rs:351-367).  The aligned slices are the append_block / anchor_block of the
- * MergePromises: pga_result_filter -> pga_slice_blocks -> pga_solve_promises is a merge in one data layout.  extract_intervals, the block
- * and node ids, group_promises / update_cigar and graph.update stay with the caller.
+ * MergePromises: pga_result_filter -> pga_plan_merge -> pga_slice_blocks -> pga_solve_promises is a merge in one data layout.
+ * extract_intervals, the block ids and group_promises / update_cigar are pga_plan_merge below; the node ids and graph.update stay with the
+ * caller.
  * Input layout as for pga_reconsensus: the members of block b are the next blocks[b].n_members entries of members[] and of nodes[], its
  * intervals the next blocks[b].n_intervals entries of intervals[], a member's edits the next n_subs / n_dels / n_inss entries of subs /
  * dels / inss.  Insertion letters are not read (only pga_ins_t.len) and not copied: a sliced insertion keeps its seq_off into the
@@ -544,6 +545,88 @@ typedef struct {
 int pga_detach_unaligned(int64_t n_blocks, const pga_rc_block_t *blocks, const pga_rc_member_t *members, const pga_sub_t *subs, const pga_del_t *dels,
                          const pga_ins_t *inss, const char *ins_seq, const pga_detach_member_t *who, pga_detach_out_t *out);
 void pga_detach_free(pga_detach_out_t *out);
+/* ---- self-merge: the front half of reweave (packages/pangraph/src/pangraph/reweave.rs:132-340, 408-443 over pangraph_interval.rs:98-255 and
+ * align/bam/cigar.rs:26-96) ----
+ * pga_plan_merge turns the filtered matches of a tree level into what the next two calls consume: the interval table of pga_slice_blocks and
+ * the (anchor, append, orientation, CIGAR) of every MergePromise.  pga_batch_align -> pga_result_filter -> pga_plan_merge -> pga_slice_blocks
+ * -> pga_solve_promises -> pga_detach_unaligned -> pga_reconsensus is self_merge (graph_merging.rs:95-172) in one data layout; node ids and
+ * the path bookkeeping of graph.update stay with the caller (pangraph_amd/reweave.py).
+ * Input: groups as pga_batch_align has them; the blocks of group g are blocks[group_off[g] .. group_off[g + 1]) in any order, block_id
+ * unique inside a group, depth = alignments.len().  matches / cigars / n_ops as pga_filter_matches takes them; qry and ref index the blocks of
+ * the match's group.  thr_len = indel_len_threshold (graph_merging.rs:142).  batch (may be NULL) with seq_index: blocks[i] is sequence
+ * seq_index[i] (hand-over order) of the resident batch, and its "not ACGT" bit plane stands in for the letters where it can.
+ * In the reference's order:
+ *   ids        aligned: XXH64, seed 0, of the six little-endian u64 words (qry block_id, qry_start, qry_end, ref block_id, ref_start, ref_end)
+ *              (reweave.rs:132-140; utils/id.rs over the derived Hash of BlockId(usize) and Interval { start, end }); an unaligned gap: XXH64 of
+ *              the three words (block_id, start, end) with the gap as created, before refinement (pangraph_interval.rs:98-132).
+ *   anchor     (reweave.rs:144-172) the deeper block; at equal depth the side with fewer bytes equal to 'N' (no other letter, no lower case)
+ *              inside its interval, ref on a tie.  route 0: depth decided.  route 1: the bit plane of the batch holds no set bit in either
+ *              interval -- it marks every letter outside ACGT, so both counts are 0 and ref wins.  route 2: the letters of both intervals
+ *              were uploaded and counted (every equal-depth match when batch == NULL).  anchor, ref_n and qry_n never depend on whether a
+ *              batch was given; route and the counters do.  ref_n = qry_n = 0 on route 0.
+ *   hits       (extract_hits, reweave.rs:202-248) a ref-side anchor keeps the match's CIGAR; a qry-side anchor gets it reversed when the
+ *              match is reverse, then I and D exchanged; the other side has none.
+ *   intervals  (create_intervals, pangraph_interval.rs:135-156) the hits of a block by ascending start; a gap before a hit where its start
+ *              is beyond the end of the hit before (or 0), a trailing gap where the last hit ends before cons_len.
+ *   refinement (pangraph_interval.rs:158-235) every decision reads the lengths of the UNREFINED list: an interval shorter than thr_len joins
+ *              its left neighbour iff left_len >= right_len (a missing neighbour has length 0), else its right one; an aligned interval can
+ *              receive from both sides.  status of a block, from the first offending interval in list order and there in the order of
+ *              check_interval_conditions: 1 the short interval is aligned, 3 its left neighbour is shorter than thr_len, 5 its right
+ *              neighbour is.  (The two "neighbour not aligned" errors cannot arise: create_intervals never emits two gaps in a row.  Nor
+ *              can 3 come first in a list it made: that left neighbour is aligned, is visited before the gap and fails with 1.)
+ *              fail_interval is that interval's index in the block's unrefined list, -1 with status 0.  The reference's reweave fails as a
+ *              whole: when any block fails, n_failed > 0, blocks[] carries status and fail_interval (n_intervals and first_interval 0),
+ *              intervals, slice_intervals, promises and cigars are NULL and their counts and the counters behind them 0.
+ *   promises   (group_promises, reweave.rs:306-340) one per match, group by group, inside a group by ascending new_block_id.  The CIGAR is
+ *              update_cigar (reweave.rs:271-304) over add_flanking_indel (cigar.rs:60-96), each step on the result of the one before:
+ *              1 anchor extend_left: D leading; 2 anchor extend_right: D trailing; 3 append extend_left: I leading if forward, else trailing;
+ *              4 append extend_right: I trailing if forward, else leading.  add_flanking_indel as written: walking from that end up to the
+ *              first M / = / X (or through the whole CIGAR when it has none), the LAST operation of the wanted kind met is lengthened;
+ *              where there is none a new operation goes to the very end of that side.  At most n_cigar + 4 operations come out.
+ * Output (freed with pga_plan_free), all exact integers:
+ *   matches[m]       one per input match: new_block_id, anchor (0 ref, 1 qry), route, ref_n, qry_n.
+ *   blocks[]         one per block with a hit, group by group and inside a group by ascending block_id (the BTreeMap order of target_blocks,
+ *                    reweave.rs:177-193, 427): block = its index in the input, its intervals are intervals[first_interval .. + n_intervals).
+ *   intervals[]      block after block, ascending start: match = the input match of an aligned interval, -1 for a gap (is_anchor, reverse 0);
+ *                    extend_left / extend_right: 0 means None (a gap is never empty, Some(0) cannot arise).  slice_intervals[] is the same
+ *                    list in the layout of pga_slice_interval_t (flip = aligned && !is_anchor && reverse): with blocks[].n_intervals it is
+ *                    the intervals argument of pga_slice_blocks, nothing is copied.
+ *   promises[]       anchor / append as (block index in the input, index into intervals[]); the CIGAR is cigars[cigar_off .. + n_cigar)
+ *                    (minimap2 packing).  A pga_promise_t is pointer arithmetic: consensus + start, end - start.
+ *   counters         matches by route, hits (2 per match), intervals before and after refinement, CIGAR operations in and out.
+ * Malformed input fails the call (-1, message in pga_last_error()); all but the three marked (device) before anything is launched: a match
+ * with qry == ref (self_merge filters those), an index outside its group, an empty hit or one outside its block, a CIGAR range outside the
+ * pool, NULL letters with cons_len > 0, two blocks of a group with one block_id, seq_index outside the batch or a length that differs from
+ * the batch's; two hits on one block that overlap (device, on the sorted list; filter_matches guarantees they do not), two matches of a
+ * group with one new_block_id (device), a CIGAR operation other than M I D = X or an operation length that would reach 2^28 after a flank
+ * (device).  Nothing the device reads depends on these being absent.  n_matches == 0 returns empty lists without a device call.
+ * The call waits for the device once.  The exception: with a batch, matches whose bit plane is not empty need their letters; they are
+ * known after that wait, are counted in a second pass and the lists are built again (a consensus with N, R, Y ... inside aligned intervals). */
+typedef struct { uint64_t block_id; const char *consensus; uint32_t cons_len, depth; } pga_plan_block_t;
+typedef struct { uint64_t new_block_id; int32_t anchor, route; uint32_t ref_n, qry_n; } pga_plan_match_t;
+typedef struct { uint64_t first_interval; int64_t fail_interval; uint32_t block, n_intervals; int32_t status, pad; } pga_plan_block_res_t;
+typedef struct {
+	uint64_t new_block_id; int64_t match;
+	uint32_t start, end;
+	int32_t aligned, is_anchor, reverse;
+	uint32_t extend_left, extend_right, pad;
+} pga_plan_interval_t;
+typedef struct {
+	uint64_t new_block_id; int64_t match;
+	uint64_t anchor_interval, append_interval, cigar_off;
+	uint32_t anchor_block, append_block, n_cigar; int32_t reverse;
+} pga_plan_promise_t;
+typedef struct { uint64_t by_depth, by_mask, by_letters, hits, intervals_before, intervals_after, cigar_in, cigar_out; } pga_plan_counters_t;
+typedef struct {
+	int64_t n_matches, n_blocks, n_intervals, n_promises, n_failed; uint64_t n_cigar;
+	pga_plan_match_t *matches; pga_plan_block_res_t *blocks;
+	pga_plan_interval_t *intervals; pga_slice_interval_t *slice_intervals;
+	pga_plan_promise_t *promises; uint32_t *cigars;
+	pga_plan_counters_t counters;
+} pga_plan_out_t;
+int pga_plan_merge(int32_t n_groups, const int64_t *group_off, const pga_plan_block_t *blocks, int64_t n_matches, const pga_match_t *matches,
+                   const uint32_t *cigars, uint64_t n_ops, uint32_t thr_len, const pga_batch_t *batch, const int64_t *seq_index, pga_plan_out_t *out);
+void pga_plan_free(pga_plan_out_t *out);
 int pga_stats_version(void);    /* == PGA_STATS_VERSION of the header the library was built with */
 /* Measurement only (no reference interface behind it): the kern_ms sums of pga_stats_t count overlapping launches on different streams
  * and batches several times.  Between pga_busy_begin() and pga_busy_end() every event-bracketed launch of the process leaves its interval

@@ -1050,6 +1050,50 @@ extern "C" int pga_merge_blocks(int64_t n_blocks, const pga_rc_block_t *blocks, 
 	} catch (std::exception &e) { pga_merge_free(out); set_err(e.what()); return -1; }
 }
 
+// ---------------------------------------------------------------- reweave's intervals and promises (pga_reweave.hip)
+namespace pga {
+struct RwResident { const uint16_t *nmask; uint64_t pos; };   // (pga_reweave_idx.h: where a block's "not ACGT" plane lies)
+void plan_merge_host(int32_t n_groups, const int64_t *group_off, const pga_plan_block_t *blocks, int64_t n_matches, const pga_match_t *matches, const uint32_t *cigars,
+                     uint64_t n_ops, uint32_t thr_len, const RwResident *res, pga_plan_out_t *out);
+}
+extern "C" void pga_plan_free(pga_plan_out_t *o)
+{
+	if (!o) return;
+	free(o->matches); free(o->blocks); free(o->intervals); free(o->slice_intervals); free(o->promises); free(o->cigars);
+	memset(o, 0, sizeof(*o));
+}
+extern "C" int pga_plan_merge(int32_t n_groups, const int64_t *group_off, const pga_plan_block_t *blocks, int64_t n_matches, const pga_match_t *matches,
+                              const uint32_t *cigars, uint64_t n_ops, uint32_t thr_len, const pga_batch_t *batch, const int64_t *seq_index, pga_plan_out_t *out)
+{
+	if (!out) { set_err("pga_plan_merge: null output"); return -1; }
+	memset(out, 0, sizeof(*out));
+	try {
+		if (n_matches < 0) throw std::runtime_error("pga_plan_merge: negative match count");
+		std::vector<pga::RwResident> res;
+		if (batch) {
+			// the sequences of the batch in hand-over order: (part, index in the part), as pga_batch_derive numbers them
+			if (n_groups < 0 || !group_off || !seq_index) throw std::runtime_error("pga_plan_merge: a batch without a group table or a sequence index");
+			std::vector<int64_t> first{0};
+			for (auto &p : batch->parts) first.push_back(first.back() + p->S.n_seq);
+			const int64_t nb = group_off[n_groups];
+			if (nb > 0 && !blocks) throw std::runtime_error("pga_plan_merge: null block list");
+			res.resize((size_t)std::max<int64_t>(nb, 0));
+			for (int64_t i = 0; i < nb; ++i) {
+				const int64_t g = seq_index[i];
+				if (g < 0 || g >= first.back()) throw std::runtime_error("pga_plan_merge: seq_index outside the batch (block " + std::to_string(i) + ")");
+				const size_t p = (size_t)(std::upper_bound(first.begin(), first.end(), g) - first.begin()) - 1;
+				const SeqSet &S = batch->parts[p]->S; const size_t li = (size_t)(g - first[p]);
+				if (S.len[li] != blocks[i].cons_len) throw std::runtime_error("pga_plan_merge: the length of block " + std::to_string(i) + " differs from its sequence in the batch");
+				if (!S.d_nmask.p) throw std::runtime_error("pga_plan_merge: the batch holds no resident bases");
+				res[(size_t)i] = pga::RwResident{S.d_nmask.p, S.off[li]};
+			}
+		}
+		if (n_matches > 0) require_device();
+		pga::plan_merge_host(n_groups, group_off, blocks, n_matches, matches, cigars, n_ops, thr_len, batch ? res.data() : nullptr, out);
+		return 0;
+	} catch (std::exception &e) { pga_plan_free(out); set_err(e.what()); return -1; }
+}
+
 // ---------------------------------------------------------------- detach_unaligned_nodes (pga_detach.hip)
 namespace pga {
 void detach_unaligned_host(int64_t n_blocks, const pga_rc_block_t *blocks, const pga_rc_member_t *members, const pga_sub_t *subs, const pga_del_t *dels, const pga_ins_t *inss,
