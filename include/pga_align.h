@@ -157,6 +157,31 @@ int pga_stage_chain_anchors(int32_t n_seq, const uint64_t *q_aoff, const uint64_
  * reloads of the backtrack's walks */
 #define PGA_N_CHAIN_ROUTES 15
 void pga_stage_chain_routes(int64_t out[PGA_N_CHAIN_ROUTES]);
+/* The post-DP kernels (pga_post.hip) on explicit inputs.  Layout contract of the three device taps: sequences are base codes 0..4; they are packed
+ * as the resident store is packed and laid out as pga_stage_extd2 lays them out -- request order, the FULL forward query of request i directly
+ * followed by its FULL target, the first base at position 0 of the store with no padding in front (request 0 has q_off == 0, the only place
+ * where the reverse-strand read below forward position 15 takes its own branch; later requests sit at whatever unaligned offsets the lengths
+ * give), the tail padded with code 4.  q_start[i] is the window's start on the ALIGNED strand (q_rev[i] = 1: the reverse complement of the
+ * forward query), t_start[i] its start on the target.  Request i's operation list is cigars[cigar_off[i] .. cigar_off[i+1]) (cigar_off has n + 1
+ * entries; operations M, I, D, N); a list that leaves its windows is refused.  a, b, sc_ambi as pga_stage_extd2 takes them.
+ * pga_stage_post_finish: mm_fix_cigar + mm_update_extra (align.c:91-167,240-289, log_gap = 1) through post_cigar_finish.  res[11 i ..] = n_cigar,
+ *   qshift, tshift, blen, mlen, n_ambi, dp_max, n_gapo, n_gap, q_span, t_span; the final list of request i is written back to
+ *   cigars[cigar_off[i] .. + n_cigar).
+ * pga_stage_post_walk: the walk of mm_test_zdrop (align.c:32-68) through post_zdrop_walk.  res[5 i ..] = max_zdrop, t0, t1, q0, q1.
+ * pga_stage_post_identity: probe i compares len[i] bases of the target from t_start[i] with len[i] bases of the aligned query strand from qs[i]
+ *   through post_identity; res[i] = mismatches, or -1 for an ambiguous base or more than m_max mismatches. */
+int pga_stage_post_finish(int32_t n, const uint8_t *const *q, const int32_t *qlen, const int32_t *q_start, const int32_t *q_rev,
+                          const uint8_t *const *t, const int32_t *tlen, const int32_t *t_start, uint32_t *cigars, const uint64_t *cigar_off,
+                          int a, int b, int sc_ambi, int gapo, int gape, int32_t *res);
+int pga_stage_post_walk(int32_t n, const uint8_t *const *q, const int32_t *qlen, const int32_t *q_start, const int32_t *q_rev,
+                        const uint8_t *const *t, const int32_t *tlen, const int32_t *t_start, const uint32_t *cigars, const uint64_t *cigar_off,
+                        int a, int b, int sc_ambi, int gapo, int gape, int32_t *res);
+int pga_stage_post_identity(int32_t n, const uint8_t *const *q, const int32_t *qlen, const int32_t *qs, const int32_t *q_rev,
+                            const uint8_t *const *t, const int32_t *tlen, const int32_t *t_start, const int32_t *len, int m_max, int32_t *res);
+/* the host's sufficient condition for mm_test_zdrop (align.c:47-89) to return 0 without a walk, from the gap costs, the match score, both
+ * thresholds, the band w of the global pass (negative: none), its zdropped flag and score, and its operation list: 1 = the walk may be skipped.
+ * A pass whose band does not cover its whole matrix is never skipped.  Host arithmetic, no device. */
+int pga_stage_zdrop_impossible(int q, int e, int q2, int e2, int a, int zdrop, int zdrop_inv, int w, int zdropped, int score, int32_t n_cigar, const uint32_t *cigar);
 /* radix_sort_128x (ksort.h:101-151, misc.c:155-159), the exact replay incl. the arrangement of equal keys: sorts every array
  * [seg_off[s], seg_off[s+1]) of the n_seg arrays in xy (two uint64 per record: x = key, y = payload) in place */
 int pga_stage_sort(int32_t n_seg, const uint64_t *seg_off, uint64_t *xy);

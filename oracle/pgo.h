@@ -90,6 +90,11 @@ void pgo_hit_sort(int *n_regs, mm_reg1_t *r);
 int pgo_squeeze_a(int n_regs, mm_reg1_t *regs, pg128 *a);
 void pgo_set_mapq(int n_regs, mm_reg1_t *regs, int min_chain_sc, int match_sc, int rep_len);
 void pgo_update_dp_max(int qlen, int n_regs, mm_reg1_t *regs, float frac, int a, int b);
+/* the walk of mm_test_zdrop (align.c:50-68) on explicit sequences (base codes): returns max_zdrop; pos[0] = target {from, to}, pos[1] = query */
+int pgo_zdrop_walk(const uint8_t *qseq, const uint8_t *tseq, uint32_t n_cigar, const uint32_t *cigar, const int8_t *mat, int q, int e, int pos[2][2]);
+/* mm_fix_cigar + mm_update_extra (align.c:91-167,240-289) of a forward-strand region spanning both sequences; the list is edited in place.
+ * out = n_cigar, qs, rs, blen, mlen, n_ambi, dp_max; returns the final n_cigar */
+int pgo_update_extra(int qspan, const uint8_t *qseq, int tspan, const uint8_t *tseq, uint32_t n_cigar, uint32_t *cigar_inout, const int8_t *mat, int q, int e, int32_t out[7]);
 mm_reg1_t *pgo_align_skeleton(const mm_mapopt_t *opt, const pgo_index_t *ix, int qlen, const char *qstr, int *n_regs, mm_reg1_t *regs, pg128 *a);
 
 /* ---- whole query (pgo_map.c) ---- */

@@ -49,24 +49,33 @@ static void track_zdrop(int32_t score, int i, int j, int32_t *max, int *max_i, i
 	} else *max = score, *max_i = i, *max_j = j;
 }
 
-static int test_zdrop(const mm_mapopt_t *opt, const uint8_t *qseq, const uint8_t *tseq, uint32_t n_cigar, const uint32_t *cigar, const int8_t *mat) /* align.c:47-89 */
+/* the walk of mm_test_zdrop (align.c:50-68): the worst drop along the list and its window, pos[0] = target {from, to}, pos[1] = query */
+static int32_t zdrop_walk(const uint8_t *qseq, const uint8_t *tseq, uint32_t n_cigar, const uint32_t *cigar, const int8_t *mat, int gap_q, int gap_e, int pos[2][2])
 {
 	int32_t score = 0, max = INT32_MIN, max_i = -1, max_j = -1, i = 0, j = 0, max_zdrop = 0;
-	int pos[2][2] = {{-1, -1}, {-1, -1}}, q_len, t_len;
+	pos[0][0] = pos[0][1] = pos[1][0] = pos[1][1] = -1;
 	for (uint32_t k = 0; k < n_cigar; ++k) {
 		uint32_t op = cigar[k] & 0xf, len = cigar[k] >> 4;
 		if (op == MM_CIGAR_MATCH) {
 			for (uint32_t l = 0; l < len; ++l) {
 				score += mat[tseq[i + l] * 5 + qseq[j + l]];
-				track_zdrop(score, i + (int)l, j + (int)l, &max, &max_i, &max_j, opt->e, &max_zdrop, pos);
+				track_zdrop(score, i + (int)l, j + (int)l, &max, &max_i, &max_j, gap_e, &max_zdrop, pos);
 			}
 			i += len, j += len;
 		} else if (op == MM_CIGAR_INS || op == MM_CIGAR_DEL || op == 3) {
-			score -= opt->q + opt->e * (int)len;
+			score -= gap_q + gap_e * (int)len;
 			if (op == MM_CIGAR_INS) j += len; else i += len;
-			track_zdrop(score, i, j, &max, &max_i, &max_j, opt->e, &max_zdrop, pos);
+			track_zdrop(score, i, j, &max, &max_i, &max_j, gap_e, &max_zdrop, pos);
 		}
 	}
+	return max_zdrop;
+}
+
+static int test_zdrop(const mm_mapopt_t *opt, const uint8_t *qseq, const uint8_t *tseq, uint32_t n_cigar, const uint32_t *cigar, const int8_t *mat) /* align.c:47-89 */
+{
+	int32_t score, i, max_zdrop;
+	int pos[2][2], q_len, t_len;
+	max_zdrop = zdrop_walk(qseq, tseq, n_cigar, cigar, mat, opt->q, opt->e, pos);
 	q_len = pos[1][1] - pos[1][0], t_len = pos[0][1] - pos[0][0];
 	if (!(opt->flag & (MM_F_SPLICE|MM_F_SR|MM_F_FOR_ONLY|MM_F_REV_ONLY)) && max_zdrop > opt->zdrop_inv && q_len < opt->max_gap && t_len < opt->max_gap) {
 		uint8_t *qseq2 = (uint8_t*)malloc((size_t)(q_len > 0 ? q_len : 1));
@@ -206,6 +215,29 @@ static void update_extra(mm_reg1_t *r, const uint8_t *qseq, const uint8_t *tseq,
 	}
 	p->dp_max = (int32_t)(max + .499);
 	assert(qoff == r->qe - r->qs && toff == r->re - r->rs);
+}
+
+/* ---- the two functions above on explicit inputs (tests of the product's post-DP kernels) ---- */
+int pgo_zdrop_walk(const uint8_t *qseq, const uint8_t *tseq, uint32_t n_cigar, const uint32_t *cigar, const int8_t *mat, int q, int e, int pos[2][2])
+{
+	return zdrop_walk(qseq, tseq, n_cigar, cigar, mat, q, e, pos);
+}
+
+int pgo_update_extra(int qspan, const uint8_t *qseq, int tspan, const uint8_t *tseq, uint32_t n_cigar, uint32_t *cigar_inout, const int8_t *mat, int q, int e, int32_t out[7])
+{
+	mm_reg1_t r;
+	mm_extra_t *p = (mm_extra_t*)calloc(sizeof(mm_extra_t) / 4 + n_cigar + 1, 4);
+	memset(&r, 0, sizeof(r));
+	r.qe = qspan, r.re = tspan;
+	p->capacity = (uint32_t)(sizeof(mm_extra_t) / 4) + n_cigar + 1;
+	p->n_cigar = n_cigar;
+	memcpy(p->cigar, cigar_inout, (size_t)n_cigar * 4);
+	r.p = p;
+	update_extra(&r, qseq, tseq, mat, (int8_t)q, (int8_t)e);
+	memcpy(cigar_inout, p->cigar, (size_t)p->n_cigar * 4);
+	out[0] = (int32_t)p->n_cigar, out[1] = r.qs, out[2] = r.rs, out[3] = r.blen, out[4] = r.mlen, out[5] = (int32_t)p->n_ambi, out[6] = p->dp_max;
+	free(p);
+	return out[0];
 }
 
 static void adjust_minier(const pgo_index_t *ix, const pg128 *a, int32_t *r, int32_t *q) /* align.c:355-371, non-HPC */

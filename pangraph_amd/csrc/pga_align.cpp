@@ -126,10 +126,15 @@ static inline bool ll_on_device(const mm_mapopt_t &opt, int q_len, int t_len)
 // much the match columns fall short of all-matches (a*L - score - gap costs; the dual-affine gap costs are bounded
 // from below by their cheapest form), mm_test_zdrop itself charges q + e*len per gap.  If even that total cannot exceed
 // zdrop (nor zdrop_inv, which gates the inversion test), the answer is 0.
-static bool zdrop_impossible(const mm_mapopt_t &opt, const DpRes &ez, const uint32_t *cigar)
+// The argument takes the pass's score for the score of the path it hands back.  That holds where the band of w diagonals
+// covers the whole matrix; a pass whose band cuts the matrix can report a score ABOVE its own trace's (ksw_extd2_sse on a
+// band of 20 over tests/post_cases.py: up to 558 above, and the walk finds 4705 where the bound says 4513), so such a
+// pass is left to the full test.  pangraph's presets never get there: bw_long * 1.5 + 1 = 150 001 diagonals, and a long
+// join's band is its longer window.  (Not static: pga_stage_zdrop_impossible, pga_api.cpp, calls it for the tests.)
+bool zdrop_impossible(const mm_mapopt_t &opt, const DpRes &ez, const uint32_t *cigar, int32_t w)
 {
 	if (ez.zdropped || ez.n_cigar <= 0 || ez.score <= -0x3fffffff) return false;
-	int64_t L = 0, g_dp = 0, g_test = 0;
+	int64_t L = 0, n_ins = 0, n_del = 0, g_dp = 0, g_test = 0;
 	for (int k = 0; k < ez.n_cigar; ++k) {
 		const int64_t op = cigar[k] & 0xf, len = cigar[k] >> 4;
 		if (op == 0) L += len;
@@ -137,8 +142,10 @@ static bool zdrop_impossible(const mm_mapopt_t &opt, const DpRes &ez, const uint
 			const int64_t c1 = opt.q + (int64_t)opt.e * len, c2 = opt.q2 + (int64_t)opt.e2 * len;
 			g_dp += c1 < c2 ? c1 : c2;
 			g_test += c1;
+			(op == 1 ? n_ins : n_del) += len;
 		} else return false;
 	}
+	if (w >= 0 && (int64_t)w < L + (n_ins > n_del ? n_ins : n_del)) return false;    // the band cuts the matrix (w < 0: ksw2's "no band")
 	const int64_t shortfall = (int64_t)opt.a * L - (int64_t)ez.score - g_dp;
 	if (shortfall < 0) return false;                 // not a plain match/mismatch matrix: leave it to the full test
 	const int64_t lim = opt.zdrop < opt.zdrop_inv ? opt.zdrop : opt.zdrop_inv;
@@ -430,7 +437,7 @@ struct Driver {
 			int final_job = sg.job1;
 			if (sg.zcode < 0 && sg.ll_job < 0) {
 				const DpRes &e1 = Q.res[(size_t)sg.job1];
-				if (zdrop_impossible(opt, e1, Q.cig[(size_t)sg.job1])) sg.zcode = 0;
+				if (zdrop_impossible(opt, e1, Q.cig[(size_t)sg.job1], sg.bw1)) sg.zcode = 0;
 				else if (sg.walk == 0) { sg.walk = 1; Q.walks.push_back(WalkAsk{&T, T.seg_k}); return false; }      // mm_test_zdrop's walk: on the device
 				else if (sg.walk == 1) return false;
 				else {

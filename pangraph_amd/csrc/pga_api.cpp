@@ -11,6 +11,7 @@
 #include <array>
 #include "pga_pipeline.h"
 #include "pga_dp.h"
+#include "pga_post.h"
 #include "../../include/pga_align.h"
 #include <atomic>
 #include <chrono>
@@ -813,6 +814,139 @@ extern "C" int pga_stage_extd2(int32_t n_jobs, const uint8_t *const *q, const in
 		*cigars = dup_out(all);
 		return 0;
 	} catch (std::exception &e) { set_err(e.what()); return -1; }
+}
+
+// ---- the post-DP kernels (pga_post.hip) and the host shortcut in front of the z-drop walk, on explicit inputs ----
+namespace pga { bool zdrop_impossible(const mm_mapopt_t &opt, const DpRes &ez, const uint32_t *cigar, int32_t w); }
+
+namespace {
+// explicit sequences (base codes 0..4) packed as the resident store is packed, laid out as pga_stage_extd2 lays them out: request order, the query
+// of request i directly followed by its target, the first base at position 0 of the store (request 0 has q_off == 0), the tail padded
+struct PostStore {
+	DBuf<uint32_t> d_pk; DBuf<uint16_t> d_nm; std::vector<uint64_t> q_off, t_off;
+	PkBases view() const { return PkBases{d_pk.p, d_nm.p}; }
+	void build(int32_t n, const uint8_t *const *q, const int32_t *qlen, const uint8_t *const *t, const int32_t *tlen)
+	{
+		std::vector<uint8_t> buf; q_off.resize((size_t)n); t_off.resize((size_t)n);
+		for (int i = 0; i < n; ++i) {
+			if (qlen[i] < 0 || tlen[i] < 0) throw std::runtime_error("post tap: negative sequence length");
+			q_off[(size_t)i] = buf.size(); buf.insert(buf.end(), q[i], q[i] + qlen[i]);
+			t_off[(size_t)i] = buf.size(); buf.insert(buf.end(), t[i], t[i] + tlen[i]);
+		}
+		buf.resize((buf.size() + 15) / 16 * 16 + 128, 4);
+		std::vector<uint32_t> pk(buf.size() / 16, 0u); std::vector<uint16_t> nm(buf.size() / 16, 0);
+		for (size_t i = 0; i < buf.size(); ++i) { const uint8_t c = buf[i]; if (c > 3) nm[i >> 4] |= (uint16_t)(1u << (i & 15)); else pk[i >> 4] |= (uint32_t)c << (2 * (i & 15)); }
+		d_pk.upload(pk, 0); d_nm.upload(nm, 0);
+	}
+};
+// an operation list must stay inside both windows: the kernels read bases wherever the list sends them
+void post_check_list(const char *who, int i, const uint32_t *cg, uint64_t n_ops, int qlen, int q_start, int q_rev, int tlen, int t_start)
+{
+	int64_t qs = 0, ts = 0;
+	for (uint64_t k = 0; k < n_ops; ++k) {
+		const uint32_t op = cg[k] & 0xf; const int64_t len = cg[k] >> 4;
+		if (op == 0) qs += len, ts += len; else if (op == 1) qs += len; else if (op == 2 || op == 3) ts += len;
+		else throw std::runtime_error(std::string(who) + ": request " + std::to_string(i) + " holds an operation other than M, I, D, N");
+	}
+	if ((q_rev != 0 && q_rev != 1) || q_start < 0 || t_start < 0 || q_start + qs > qlen || t_start + ts > tlen)
+		throw std::runtime_error(std::string(who) + ": the list of request " + std::to_string(i) + " leaves its windows");
+}
+}
+
+extern "C" int pga_stage_post_finish(int32_t n, const uint8_t *const *q, const int32_t *qlen, const int32_t *q_start, const int32_t *q_rev,
+                                     const uint8_t *const *t, const int32_t *tlen, const int32_t *t_start, uint32_t *cigars, const uint64_t *cigar_off,
+                                     int a, int b, int sc_ambi, int gapo, int gape, int32_t *res)
+{
+	try {
+		require_device();
+		if (n < 0 || (n && (!q || !qlen || !q_start || !q_rev || !t || !tlen || !t_start || !cigar_off || !res))) throw std::runtime_error("pga_stage_post_finish: null argument");
+		if (!n) return 0;
+		for (int i = 0; i < n; ++i) {
+			if (cigar_off[i + 1] < cigar_off[i]) throw std::runtime_error("pga_stage_post_finish: cigar_off descends");
+			post_check_list("pga_stage_post_finish", i, cigars + cigar_off[i], cigar_off[i + 1] - cigar_off[i], qlen[i], q_start[i], q_rev[i], tlen[i], t_start[i]);
+		}
+		PostStore S; S.build(n, q, qlen, t, tlen);
+		std::vector<PostFin> reqs((size_t)n);
+		for (int i = 0; i < n; ++i) {
+			PostFin &F = reqs[(size_t)i]; memset(&F, 0, sizeof(F));
+			F.t_off = S.t_off[(size_t)i] + (uint64_t)t_start[i]; F.q_off = S.q_off[(size_t)i]; F.qlen_full = qlen[i]; F.q_start = q_start[i]; F.q_rev = q_rev[i];
+			F.n_cigar = (uint32_t)(cigar_off[i + 1] - cigar_off[i]); F.cig_off = cigar_off[i];
+		}
+		const size_t n_ops = (size_t)cigar_off[n];
+		PinVec<uint32_t> cg; cg.resize(n_ops);
+		if (n_ops) memcpy(cg.data(), cigars, n_ops * sizeof(uint32_t));
+		a = a < 0 ? -a : a; b = b > 0 ? -b : b; sc_ambi = sc_ambi > 0 ? -sc_ambi : sc_ambi;
+		DpParams P{gapo, gape, 0, 0, a, b, sc_ambi, 0};
+		std::vector<PostFinRes> out;
+		post_cigar_finish(S.view(), reqs, cg, P, out, 0);
+		static_assert(sizeof(PostFinRes) == 11 * sizeof(int32_t), "pga_stage_post_finish hands the eleven fields out as they lie");
+		memcpy(res, out.data(), (size_t)n * sizeof(PostFinRes));
+		if (n_ops) memcpy(cigars, cg.data(), n_ops * sizeof(uint32_t));
+		return 0;
+	} catch (std::exception &e) { set_err(e.what()); return -1; }
+}
+
+extern "C" int pga_stage_post_walk(int32_t n, const uint8_t *const *q, const int32_t *qlen, const int32_t *q_start, const int32_t *q_rev,
+                                   const uint8_t *const *t, const int32_t *tlen, const int32_t *t_start, const uint32_t *cigars, const uint64_t *cigar_off,
+                                   int a, int b, int sc_ambi, int gapo, int gape, int32_t *res)
+{
+	try {
+		require_device();
+		if (n < 0 || (n && (!q || !qlen || !q_start || !q_rev || !t || !tlen || !t_start || !cigar_off || !res))) throw std::runtime_error("pga_stage_post_walk: null argument");
+		if (!n) return 0;
+		for (int i = 0; i < n; ++i) {
+			if (cigar_off[i + 1] < cigar_off[i]) throw std::runtime_error("pga_stage_post_walk: cigar_off descends");
+			post_check_list("pga_stage_post_walk", i, cigars + cigar_off[i], cigar_off[i + 1] - cigar_off[i], qlen[i], q_start[i], q_rev[i], tlen[i], t_start[i]);
+		}
+		PostStore S; S.build(n, q, qlen, t, tlen);
+		std::vector<PostWalk> reqs((size_t)n);
+		for (int i = 0; i < n; ++i) {
+			PostWalk &W = reqs[(size_t)i]; memset(&W, 0, sizeof(W));
+			W.t_off = S.t_off[(size_t)i] + (uint64_t)t_start[i]; W.q_off = S.q_off[(size_t)i]; W.qlen_full = qlen[i]; W.qs = q_start[i]; W.q_rev = q_rev[i];
+			W.n_cigar = (uint32_t)(cigar_off[i + 1] - cigar_off[i]); W.cig_off = cigar_off[i];
+		}
+		std::vector<uint32_t> cg(cigars, cigars + cigar_off[n]);
+		a = a < 0 ? -a : a; b = b > 0 ? -b : b; sc_ambi = sc_ambi > 0 ? -sc_ambi : sc_ambi;
+		DpParams P{gapo, gape, 0, 0, a, b, sc_ambi, 0};
+		std::vector<PostWalkRes> out;
+		post_zdrop_walk(S.view(), reqs, cg, P, out, 0);
+		static_assert(sizeof(PostWalkRes) == 5 * sizeof(int32_t), "pga_stage_post_walk hands the five fields out as they lie");
+		memcpy(res, out.data(), (size_t)n * sizeof(PostWalkRes));
+		return 0;
+	} catch (std::exception &e) { set_err(e.what()); return -1; }
+}
+
+extern "C" int pga_stage_post_identity(int32_t n, const uint8_t *const *q, const int32_t *qlen, const int32_t *qs, const int32_t *q_rev,
+                                       const uint8_t *const *t, const int32_t *tlen, const int32_t *t_start, const int32_t *len, int m_max, int32_t *res)
+{
+	try {
+		require_device();
+		if (n < 0 || (n && (!q || !qlen || !qs || !q_rev || !t || !tlen || !t_start || !len || !res))) throw std::runtime_error("pga_stage_post_identity: null argument");
+		if (!n) return 0;
+		for (int i = 0; i < n; ++i)
+			if ((q_rev[i] != 0 && q_rev[i] != 1) || len[i] < 0 || qs[i] < 0 || t_start[i] < 0 || (int64_t)qs[i] + len[i] > qlen[i] || (int64_t)t_start[i] + len[i] > tlen[i])
+				throw std::runtime_error("pga_stage_post_identity: probe " + std::to_string(i) + " leaves its sequences");
+		PostStore S; S.build(n, q, qlen, t, tlen);
+		PinVec<PostProbe> pr; pr.resize((size_t)n);
+		for (int i = 0; i < n; ++i) {
+			PostProbe &B = pr.data()[i]; memset(&B, 0, sizeof(B));
+			B.t_off = S.t_off[(size_t)i] + (uint64_t)t_start[i]; B.q_off = S.q_off[(size_t)i]; B.qlen_full = qlen[i]; B.qs = qs[i]; B.n = len[i]; B.q_rev = q_rev[i];
+		}
+		PinVec<int32_t> out;
+		post_identity(S.view(), pr, m_max, out, 0);
+		memcpy(res, out.data(), (size_t)n * sizeof(int32_t));
+		return 0;
+	} catch (std::exception &e) { set_err(e.what()); return -1; }
+}
+
+// host arithmetic: no device is asked for
+extern "C" int pga_stage_zdrop_impossible(int q, int e, int q2, int e2, int a, int zdrop, int zdrop_inv, int w, int zdropped, int score, int32_t n_cigar, const uint32_t *cigar)
+{
+	mm_mapopt_t mo; memset(&mo, 0, sizeof(mo));
+	mo.q = q, mo.e = e, mo.q2 = q2, mo.e2 = e2, mo.a = a, mo.zdrop = zdrop, mo.zdrop_inv = zdrop_inv;
+	DpRes R; memset(&R, 0, sizeof(R));
+	R.zdropped = zdropped, R.score = score, R.n_cigar = n_cigar;
+	return zdrop_impossible(mo, R, cigar, w) ? 1 : 0;
 }
 
 extern "C" void pga_stage_dp_routes(int64_t by_class[14], int64_t handed_back[2]) { dp_routes_take(by_class, handed_back); }
