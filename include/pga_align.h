@@ -484,8 +484,9 @@ int pga_core_alignment(int64_t n_blocks, const pga_rc_block_t *blocks, const pga
 /* ---- simplify: the block concatenations of remove_transitive_edges (packages/pangraph/src/circularize/merge_blocks.rs:92-148) ----
  * pga_merge_blocks performs any number of independent concatenations in one call: per edge concatenate_alignments of the left and the right
  * block, each taken as it is or through PangraphBlock::reverse_complement (pangraph_block.rs:63-75) first.  orient_merging_edge,
- * find_node_pairings, the node ids and the path / node updates stay with the caller (pangraph_amd/simplify.py).  Blocks, members and edits
- * in the layout of pga_reconstruct; a block may be named by several edges, inputs are only read.
+ * find_node_pairings, the node ids and the path / node updates are not part of this call: pga_plan_simplify (below) does them for a whole
+ * round and hands over `edges` and `partner` as this call takes them; pangraph_amd/simplify.py also keeps them as host functions.  Blocks,
+ * members and edits in the layout of pga_reconstruct; a block may be named by several edges, inputs are only read.
  * partner: for edge e the next blocks[left].n_members entries; entry k is the index, inside the right block, of the member joined with
  * the k-th member of the left block (node_map of concatenate_alignments) -- a permutation of the right block's members.
  * Per edge, exactly as the reference (the list order is observable: its Edit compares Vecs):
@@ -520,6 +521,73 @@ typedef struct {
 int pga_merge_blocks(int64_t n_blocks, const pga_rc_block_t *blocks, const pga_rc_member_t *members, const pga_sub_t *subs, const pga_del_t *dels,
                      const pga_ins_t *inss, const char *ins_seq, int64_t n_edges, const pga_merge_edge_t *edges, const uint32_t *partner, pga_merge_out_t *out);
 void pga_merge_free(pga_merge_out_t *out);
+
+/* ---- simplify: the path side of one round of remove_transitive_edges (circularize/circularize.rs:11-76 find_transitive_edges / count_edges,
+ * circularize/merge_blocks.rs:33-89 orient_merging_edge / find_node_pairings, :196-234 graph_merging_update_paths / _nodes) ----
+ * pga_plan_simplify counts the edges of every path, lists the transitive ones, chooses a round of disjoint edges, orients them, pairs the
+ * nodes of every chosen edge, makes the new nodes with their ids and rewrites the paths: what pga_merge_blocks leaves to its caller, for all
+ * edges of the round in one call.  Input flat and only read:
+ *   blocks[n_blocks]   the alive ones in strictly ascending block_id, so that index order is the reference's BTreeMap order; entries with
+ *                      alive == 0 are skipped and no node may name one.  depth = alignments.len().
+ *   paths[n_paths]     ascending path_id; its nodes are nodes[node_off .. node_off + n_nodes), node_off the running sum; n_nodes == 0 is legal.
+ *   nodes[n_nodes]     path after path.  block: index into blocks; member: the node's slot in that block's member order, the numbering of
+ *                      the block arrays given to pga_merge_blocks.  Every (block, member) slot is named by exactly one node.
+ *   sched[n_sched]     NULL: the defined round -- the transitive edges in sorted order, each taken while both of its blocks are unused in
+ *                      the round.  Otherwise the round's edges, in either orientation; each must be transitive and no block named twice.
+ *   flags              PGA_TOPO_EDGES_ONLY: stop behind the transitive list.  PGA_TOPO_COUNTS: also return every counted edge (edge_counts).
+ * An EDGE is the pair (block, strand) -> (block, strand) of a node and its successor on the path (the first node behind the last of a
+ * circular path), in Edge::conventional_orientation: as it stands when b1 < b2 (b1 == b2: when s1 is forward), else inverted
+ * ((b2, !s2), (b1, !s1)).  Strands: 0 forward, 1 reverse.  An edge is transitive when b1 != b2 and count == depth[b1] == depth[b2].
+ * Output (freed with pga_topo_free), all exact integers:
+ *   transitive[]       by (b1, b2, s1, s2), block indices.  Two different edges between the same two blocks both appear.
+ *   edge_counts[]      (PGA_TOPO_COUNTS) every edge seen, the same order, self-loops included.
+ *   round[]            one per chosen edge in the order chosen: the oriented edge, anchor first (the longer consensus, on a tie the smaller
+ *                      block_id), its index in transitive[], `merge` = (left, right, left_rc, right_rc) by merge_blocks.rs:100-111
+ *                      ((anchor, other, 0, rc) when the anchor's strand is forward, else (other, anchor, rc, 0), rc = the strands
+ *                      differ) as block indices of THIS graph, and partner_off.
+ *   partner[]          edge after edge; entry partner_off + k is the slot in the right block joined with slot k of the left block: the
+ *                      partner argument of pga_merge_blocks in the same edge order.
+ *   new_nodes[]        same indexing: node_id = XXH64, seed 0, of the five little-endian u64 words (anchor block_id, path_id, reverse,
+ *                      pos0, pos1) (PangraphNode::new(None, ..)); block the anchor's index, member k, reverse the strand of the pair's
+ *                      anchor-block node, (pos0, pos1) = (pos0 of the pair's first node in path order, pos1 of its second).
+ *                      old_left[] / old_right[]: the ids of the left-block and the right-block node it replaces.
+ *   paths, nodes, blocks   the graph behind the round in the input layout (n_paths, n_nodes_out, n_blocks entries): the anchor-block node
+ *                      of a pair replaced in place by the new node, the other dropped; the anchor block with cons_len the sum and its
+ *                      depth, the other block alive = 0, depth = 0, cons_len = 0.  They are the next call's input by pointer.
+ *                      With n_round == 0 the three are NULL: the graph is unchanged.
+ * The transitive list comes back to the host, the round is chosen there (sequential by definition, O(transitive edges)), and the pairing
+ * and the splice follow on the device.
+ * Malformed input fails the call (-1, message in pga_last_error(), no output).  Before anything is launched: alive block ids not strictly
+ * ascending, path ids not ascending, a node naming a block out of range or a dead block, member >= depth, n_nodes of the paths not summing
+ * to the node count or node_off not the running sum, 2^31 or more nodes, blocks or paths, a merged consensus of 2^32 letters or more, a
+ * sched edge that is not transitive or names a block twice, n_sched == 0 with a non-NULL sched.  On the device, before any index derived
+ * from it is used: a (block, member) slot named by no node or by two, nodes of a block not summing to its depth; behind the pairing: a slot of
+ * a partner list left unwritten.  n_paths == 0 or n_nodes == 0 returns empty lists without a device call. */
+#define PGA_TOPO_EDGES_ONLY 1u
+#define PGA_TOPO_COUNTS 2u
+#define PGA_TOPO_TILE 1024       /* path positions per workgroup of the splice's scan */
+typedef struct { uint64_t block_id; uint32_t cons_len, depth; int32_t alive, pad; } pga_topo_block_t;
+typedef struct { uint64_t path_id, node_off; uint32_t n_nodes; int32_t circular; } pga_topo_path_t;
+typedef struct { uint64_t node_id, pos0, pos1; uint32_t block, member; int32_t reverse, pad; } pga_topo_node_t;
+typedef struct { uint32_t b1; int32_t s1; uint32_t b2; int32_t s2; } pga_topo_sched_t;          /* ((block, reverse), (block, reverse)) */
+typedef struct { uint32_t b1, b2; int32_t s1, s2; uint32_t count, pad; } pga_topo_edge_t;
+typedef struct {
+	uint32_t anchor, other; int32_t anchor_rev, other_rev;    /* the oriented edge */
+	uint32_t transitive, pad;
+	pga_merge_edge_t merge;
+	uint64_t partner_off;
+} pga_topo_round_t;
+typedef struct {
+	int64_t n_transitive, n_counts, n_round, n_partner, n_blocks, n_paths, n_nodes;
+	pga_topo_edge_t *transitive, *edge_counts;
+	pga_topo_round_t *round;
+	uint32_t *partner;
+	pga_topo_node_t *new_nodes; uint64_t *old_left, *old_right;
+	pga_topo_path_t *paths; pga_topo_node_t *nodes; pga_topo_block_t *blocks;
+} pga_topo_out_t;
+int pga_plan_simplify(int64_t n_blocks, const pga_topo_block_t *blocks, int64_t n_paths, const pga_topo_path_t *paths, int64_t n_nodes,
+                      const pga_topo_node_t *nodes, int64_t n_sched, const pga_topo_sched_t *sched, uint32_t flags, pga_topo_out_t *out);
+void pga_topo_free(pga_topo_out_t *out);
 
 /* ---- self-merge: detach_unaligned_nodes (packages/pangraph/src/pangraph/detach_unaligned.rs:24-114) ----
  * pga_detach_unaligned takes the members without an aligned position out of their blocks and makes each a singleton block of its own

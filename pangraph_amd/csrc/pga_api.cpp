@@ -1184,6 +1184,30 @@ extern "C" int pga_merge_blocks(int64_t n_blocks, const pga_rc_block_t *blocks, 
 	} catch (std::exception &e) { pga_merge_free(out); set_err(e.what()); return -1; }
 }
 
+// ---------------------------------------------------------------- simplify's edges, pairings and paths (pga_topo.hip)
+namespace pga {
+void plan_simplify_host(int64_t n_blocks, const pga_topo_block_t *blocks, int64_t n_paths, const pga_topo_path_t *paths, int64_t n_nodes, const pga_topo_node_t *nodes,
+                        int64_t n_sched, const pga_topo_sched_t *sched, uint32_t flags, pga_topo_out_t *out);
+}
+extern "C" void pga_topo_free(pga_topo_out_t *o)
+{
+	if (!o) return;
+	free(o->transitive); free(o->edge_counts); free(o->round); free(o->partner); free(o->new_nodes); free(o->old_left); free(o->old_right);
+	free(o->paths); free(o->nodes); free(o->blocks);
+	memset(o, 0, sizeof(*o));
+}
+extern "C" int pga_plan_simplify(int64_t n_blocks, const pga_topo_block_t *blocks, int64_t n_paths, const pga_topo_path_t *paths, int64_t n_nodes,
+                                 const pga_topo_node_t *nodes, int64_t n_sched, const pga_topo_sched_t *sched, uint32_t flags, pga_topo_out_t *out)
+{
+	if (!out) { set_err("pga_plan_simplify: null output"); return -1; }
+	memset(out, 0, sizeof(*out));
+	try {
+		if (n_paths > 0 && n_nodes > 0) require_device();
+		pga::plan_simplify_host(n_blocks, blocks, n_paths, paths, n_nodes, nodes, n_sched, sched, flags, out);
+		return 0;
+	} catch (std::exception &e) { pga_topo_free(out); set_err(e.what()); return -1; }
+}
+
 // ---------------------------------------------------------------- reweave's intervals and promises (pga_reweave.hip)
 namespace pga {
 struct RwResident { const uint16_t *nmask; uint64_t pos; };   // (pga_reweave_idx.h: where a block's "not ACGT" plane lies)

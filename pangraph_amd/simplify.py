@@ -2,6 +2,7 @@
 (Pangraph::remove_path, pangraph/pangraph.rs:110-132) and transitive edges are merged until none is left (circularize/circularize.rs:11-76,
 circularize/merge_blocks.rs:15-234).  The graph bookkeeping, O(nodes), is done here; the block concatenations -- consensus letters and edit
 lists -- are `pga_merge_blocks` (include/pga_align.h), one call per ROUND of disjoint edges.  ctypes only; the HIP library does the work.
+With simplify(topology="device") the graph bookkeeping of a round is one `pga_plan_simplify` call as well (topology.py).
 
 The reference merges `find_transitive_edges(graph).first()` of a HashMap iteration until none is left: its order is undefined, and for chains
 the orientation and the id of the final block depend on it.  The DEFINED order here: in every round the transitive edges are sorted by
@@ -280,16 +281,93 @@ class _DeviceRounds:
             self.prev = None
 
 
-def simplify(graph, focal_names, dll=None, schedule=None, merge=None, trace=None):
+def _simplify_planned(g, order, dll, schedule, merge, trace, topology):
+    """simplify()'s loop with the path side in pga_plan_simplify (topology.py): the graph is packed once, every round is one call whose
+    output arrays are the next round's input, `round` and `partner` feed the block merge as they come, and the dicts are rebuilt once at
+    the end.  Inside the loop only blocks are touched on the host: O(merged members), no walk over paths or nodes."""
+    from . import topology as tp
+    args = tp.pack_graph(g, order)
+    planner = tp.DevicePlanner(args, dll) if topology == "device" else tp.StandInPlanner(args, topology)
+    bids = sorted(g["blocks"])
+    index = {b: i for i, b in enumerate(bids)}
+    strand = lambda rev: "-" if rev else "+"
+    blocks = {"blocks": {b: {"consensus": g["blocks"][b]["consensus"], "alignments": [g["blocks"][b]["alignments"][n] for n in order[b]]} for b in bids}}
+    slots = {b: range(len(order[b])) for b in bids}                               # (a block's members are named by their slot from here on)
+    device, rounds, lists = None, [], []
+    try:
+        while True:
+            sched = None
+            if schedule is not None and len(rounds) < len(schedule):
+                if not planner.step(flags=tp.EDGES_ONLY)["transitive"]:
+                    break
+                given = [tuple(map(tuple, e)) for e in schedule[len(rounds)]]
+                if not given or any(b not in index or b not in blocks["blocks"] for e in given for b in (e[0][0], e[1][0])):
+                    raise ValueError("a round of the schedule is empty or names a block that does not exist")
+                sched = [(index[b1], s1 == "-", index[b2], s2 == "-") for (b1, s1), (b2, s2) in given]
+            try:
+                res = planner.step(sched)
+            except batch.PgaError as err:
+                if sched is None:
+                    raise
+                raise ValueError(f"a round of the schedule names an edge that is not transitive, or uses a block twice ({err})")
+            transitive =[((bids[b1], strand(s1)), (bids[b2], strand(s2))) for b1, b2, s1, s2, _ in res["transitive"]]
+            if not transitive:
+                break
+            lists.append(transitive)
+            jobs = []
+            for r in res["round"]:
+                left, right, left_rc, right_rc = r["merge"]
+                jobs.append({"left": bids[left], "right": bids[right], "left_rc": bool(left_rc), "right_rc": bool(right_rc), "anchor": bids[r["anchor"]], "other": bids[r["other"]],
+                             "partner": list(res["partner"][r["partner_off"]:r["partner_off"] + len(slots[bids[left]])])})
+            if merge is not None:
+                named = [b for j in jobs for b in (j["left"], j["right"])]
+                at = {b: i for i, b in enumerate(named)}
+                out = merge([{"consensus": blocks["blocks"][b]["consensus"], "members": blocks["blocks"][b]["alignments"]} for b in named],
+                            [dict(j, left=at[j["left"]], right=at[j["right"]]) for j in jobs])
+            else:
+                device = device or _DeviceRounds(dll)
+                out = device(blocks, slots, jobs)
+            for j, r in zip(jobs, out):
+                if r["status"] != 0:
+                    raise SimplifyError(f"blocks {j['anchor']} and {j['other']}: a letter without a complement")
+                del blocks["blocks"][j["left"]], blocks["blocks"][j["right"]], slots[j["other"]]
+                blocks["blocks"][j["anchor"]] = {"consensus": r["consensus"], "alignments": r["members"]}
+                slots[j["anchor"]] = range(len(r["members"]))
+            rounds.append(given if sched is not None else [transitive[r["transitive"]] for r in res["round"]])
+        b_list, p_list, n_list = planner.lists()
+    finally:
+        planner.close()
+        if device is not None:
+            if trace is not None:
+                trace["zero_copy"] = list(device.zero_copy)
+            device.close()
+    if trace is not None:
+        trace["rounds"], trace["transitive"] = rounds, lists
+    # the dicts, once, from the final arrays
+    out = {"paths": {}, "nodes": {}, "blocks": {bid: {"consensus": blocks["blocks"][bid]["consensus"], "alignments": {}} for bid, _, _, alive in b_list if alive}}
+    for pid, off, n, _ in p_list:
+        out["paths"][pid] = dict(g["paths"][pid], nodes=[x[0] for x in n_list[off:off + n]])
+        for nid, pos0, pos1, b, member, rev in n_list[off:off + n]:
+            out["nodes"][nid] = {"block_id": bids[b], "path_id": pid, "strand": strand(rev), "position": (pos0, pos1)}
+            out["blocks"][bids[b]]["alignments"][nid] = blocks["blocks"][bids[b]]["alignments"][member]
+    return out
+
+
+def simplify(graph, focal_names, dll=None, schedule=None, merge=None, trace=None, topology=None):
     """graph: a parsed pangraph JSON; focal_names: the paths to keep.  -> the simplified graph in the shape of normalize().
     schedule: explicit first rounds, [[edge, ...], ...] with edge = ((block id, strand), (block id, strand)); every round's edges must be
     transitive and share no block; behind the last of them the defined order goes on.  merge: stands in for the device call (blocks, edges as merge_blocks takes them -> its result).
-    trace: a dict that receives "rounds" (the rounds taken) and "zero_copy" (per device round: its input was the previous output)."""
+    trace: a dict that receives "rounds" (the rounds taken) and "zero_copy" (per device round: its input was the previous output).
+    topology: None -- the graph level is the host functions of this module; "device" -- it is pga_plan_simplify, one call per round
+    (topology.py), or a callable standing in for that call (blocks, paths, nodes, sched, flags as lists -> what PlanOut.to_lists() gives);
+    trace then also receives "transitive", the transitive edges of every round taken."""
     g = normalize(graph)
     focal = set(focal_names)
     for pid in [pid for pid in sorted(g["paths"]) if g["paths"][pid]["name"] not in focal]:
         remove_path(g, pid)
     order = {b: sorted(blk["alignments"]) for b, blk in g["blocks"].items()}      # the member order of every block in the arrays
+    if topology is not None:
+        return _simplify_planned(g, order, dll, schedule, merge, trace, topology)
     device = None
     rounds = []
     try:
