@@ -342,8 +342,8 @@ int pga_stage_promise_jobs(int64_t n_promises, const pga_promise_t *promises, co
  * (new_position_circular / _non_circular, new_strandedness, slice.rs:55-101), and the member left out of the slice when its alignment has
  * become empty (Edit::is_empty_alignment, edits.rs:351-367).  The aligned slices are the append_block / anchor_block of the
  * MergePromises: pga_result_filter -> pga_plan_merge -> pga_slice_blocks -> pga_solve_promises is a merge in one data layout.
- * extract_intervals, the block ids and group_promises / update_cigar are pga_plan_merge below; the node ids and graph.update stay with the
- * caller.
+ * extract_intervals, the block ids and group_promises / update_cigar are pga_plan_merge below; the node ids and graph.update are
+ * pga_apply_merge further below.
  * Input layout as for pga_reconsensus: the members of block b are the next blocks[b].n_members entries of members[] and of nodes[], its
  * intervals the next blocks[b].n_intervals entries of intervals[], a member's edits the next n_subs / n_dels / n_inss entries of subs /
  * dels / inss.  Insertion letters are not read (only pga_ins_t.len) and not copied: a sliced insertion keeps its seq_off into the
@@ -643,7 +643,7 @@ void pga_detach_free(pga_detach_out_t *out);
  * pga_plan_merge turns the filtered matches of a tree level into what the next two calls consume: the interval table of pga_slice_blocks and
  * the (anchor, append, orientation, CIGAR) of every MergePromise.  pga_batch_align -> pga_result_filter -> pga_plan_merge -> pga_slice_blocks
  * -> pga_solve_promises -> pga_detach_unaligned -> pga_reconsensus is self_merge (graph_merging.rs:95-172) in one data layout; node ids and
- * the path bookkeeping of graph.update stay with the caller (pangraph_amd/reweave.py).
+ * the path bookkeeping of graph.update are pga_apply_merge below (pangraph_amd/apply.py; the host loop of pangraph_amd/reweave.py is its restatement).
  * Input: groups as pga_batch_align has them; the blocks of group g are blocks[group_off[g] .. group_off[g + 1]) in any order, block_id
  * unique inside a group, depth = alignments.len().  matches / cigars / n_ops as pga_filter_matches takes them; qry and ref index the blocks of
  * the match's group.  thr_len = indel_len_threshold (graph_merging.rs:142).  batch (may be NULL) with seq_index: blocks[i] is sequence
@@ -720,7 +720,58 @@ typedef struct {
 int pga_plan_merge(int32_t n_groups, const int64_t *group_off, const pga_plan_block_t *blocks, int64_t n_matches, const pga_match_t *matches,
                    const uint32_t *cigars, uint64_t n_ops, uint32_t thr_len, const pga_batch_t *batch, const int64_t *seq_index, pga_plan_out_t *out);
 void pga_plan_free(pga_plan_out_t *out);
-int pga_stats_version(void);    /* == PGA_STATS_VERSION of the header the library was built with */
+
+/* ---- self-merge: the graph update behind the slices (split_block's n_new / b_new, reweave.rs:359-401; Pangraph::update, pangraph.rs:68-107,
+ * applied block after block, reweave.rs:445-450; the insertion of the merged blocks, graph_merging.rs:156-165) ----
+ * pga_apply_merge replaces, on the flat graph of pga_plan_simplify, every node of a cut block by the nodes of its kept slices, makes those
+ * nodes with their ids, and builds the block table behind the round with the member slots of every new block.
+ * The graph (the first six arguments) is that of pga_plan_simplify, with its rules.  The cut is what the two calls before produced, as it stands:
+ *   cut[n_cut]     one per plan.blocks[k]: block = its index in THIS graph, first_interval / n_intervals the record's own (first_interval is
+ *                  the running sum of n_intervals: intervals[] is numbered as slices[] is).
+ *   intervals      plan.intervals; read: new_block_id, start, end, aligned, is_anchor.
+ *   slices, members   the output of the pga_slice_blocks call whose blocks were given in the order of plan.blocks[]; the member order of that
+ *                  call is the block's member order, the `member` slot of the graph's nodes.
+ * Output (freed with pga_apply_free), all exact integers:
+ *   new_nodes[k]   belongs to slice.members[k]: node_id = XXH64, seed 0, of the five little-endian u64 words (new_block_id, path_id, reverse,
+ *                  pos_start, pos_end), reverse and the position the slice member's; block / member: its place in the graph after.
+ *                  old_node[k]: the id of the node it replaces.
+ *   paths, nodes   a node of a block that is not cut stays (with its slot, its block index translated); a node (block b, member m) of a cut
+ *                  block is replaced in place by the new nodes of the kept members with .member == m over b's intervals in interval order,
+ *                  in reversed order when the OLD node is reverse; no kept member: the position disappears, a path may become empty.
+ *                  path_id and circular unchanged, node_off the new running sum.
+ *   blocks[]       the table after, alive blocks only, strictly ascending block_id (unsigned): the surviving alive blocks, one block per
+ *                  unaligned interval (cons_len = end - start; depth 0 when its slice kept no member), one per new_block_id of an aligned
+ *                  anchor / append pair (cons_len of the anchor interval, depth = kept members of both).  block_map[old index] = new index,
+ *                  UINT32_MAX for a cut block and for a dead entry (dead entries are dropped).
+ *   new_blocks[]   the blocks the call made, by ascending id: block = index in blocks[]; kind 0 an unaligned slice (interval_a; interval_b 0),
+ *                  kind 1 a merged block (interval_a the anchor, interval_b the append).  A node's member in a new block is the rank of its
+ *                  node_id among the block's, ascending (the BTreeMap order of alignment_insert); member_src[member_off + s] is the index
+ *                  into slice.members[] that fills slot s: the gather list for the block arrays.
+ *   (n_blocks, blocks, n_paths, paths, n_nodes, nodes) are the first six arguments of pga_plan_simplify and of the next pga_apply_merge.
+ * n_cut == 0 returns zero counts and NULL arrays: the graph is unchanged.
+ * Malformed input fails the call (-1, message in pga_last_error(), no output).  Before anything is launched: what pga_plan_simplify refuses
+ * about the graph on the host, depths that do not sum to the node count, a cut block out of range, dead or named twice, n_intervals == 0,
+ * first_interval not the running sum, intervals of a block not ascending and disjoint (or empty), an aligned interval without its partner
+ * of the same new_block_id and the opposite is_anchor, member_off of a slice not the running sum of n_kept or n_kept above the block's
+ * depth (n_kept not matching members[]), 2^31 or more nodes, blocks, intervals or members-times-intervals after.  On the device, before any
+ * index derived from it is used: a (block, member) slot named by no node or by two, a slice member with member >= depth of its block, a
+ * member kept twice in one interval, a new block_id equal to a surviving one or to another new one (the reference panics "Conflicting
+ * key"), two equal node ids inside one block after.  The call waits for the device three times: the checks, the splice's total, the output. */
+typedef struct { uint32_t block, n_intervals; uint64_t first_interval; } pga_apply_cut_t;
+typedef struct { uint32_t block; int32_t kind; uint64_t interval_a, interval_b, member_off; } pga_apply_block_t;
+typedef struct {
+	int64_t n_new_nodes, n_new_blocks, n_blocks, n_paths, n_nodes;
+	pga_topo_node_t *new_nodes; uint64_t *old_node;          /* one per kept slice member, indexed as slice.members[] */
+	pga_apply_block_t *new_blocks; uint64_t *member_src;     /* per new block, slot after slot: index into slice.members[] */
+	uint32_t *block_map;                                     /* old block index -> new index, UINT32_MAX for a cut block */
+	pga_topo_path_t *paths; pga_topo_node_t *nodes; pga_topo_block_t *blocks;   /* the graph after, input layout */
+} pga_apply_out_t;
+int pga_apply_merge(int64_t n_blocks, const pga_topo_block_t *blocks, int64_t n_paths, const pga_topo_path_t *paths,
+                    int64_t n_nodes, const pga_topo_node_t *nodes,
+                    int64_t n_cut, const pga_apply_cut_t *cut, const pga_plan_interval_t *intervals,
+                    const pga_slice_res_t *slices, const pga_slice_member_t *members, pga_apply_out_t *out);
+void pga_apply_free(pga_apply_out_t *out);
+int pga_stats_version(void);   /* == PGA_STATS_VERSION of the header the library was built with */
 /* Measurement only (no reference interface behind it): the kern_ms sums of pga_stats_t count overlapping launches on different streams
  * and batches several times.  Between pga_busy_begin() and pga_busy_end() every event-bracketed launch of the process leaves its interval
  * on the device clock; pga_busy_end writes, for each of the PGA_N_KERNELS kernel families of pga_stats_t (same order), the length in ms of

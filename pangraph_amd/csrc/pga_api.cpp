@@ -1208,6 +1208,31 @@ extern "C" int pga_plan_simplify(int64_t n_blocks, const pga_topo_block_t *block
 	} catch (std::exception &e) { pga_topo_free(out); set_err(e.what()); return -1; }
 }
 
+// ---------------------------------------------------------------- reweave's graph update on the flat graph (pga_apply.hip)
+namespace pga {
+void apply_merge_host(int64_t n_blocks, const pga_topo_block_t *blocks, int64_t n_paths, const pga_topo_path_t *paths, int64_t n_nodes, const pga_topo_node_t *nodes,
+                      int64_t n_cut, const pga_apply_cut_t *cut, const pga_plan_interval_t *intervals, const pga_slice_res_t *slices, const pga_slice_member_t *members,
+                      pga_apply_out_t *out);
+}
+extern "C" void pga_apply_free(pga_apply_out_t *o)
+{
+	if (!o) return;
+	free(o->new_nodes); free(o->old_node); free(o->new_blocks); free(o->member_src); free(o->block_map); free(o->paths); free(o->nodes); free(o->blocks);
+	memset(o, 0, sizeof(*o));
+}
+extern "C" int pga_apply_merge(int64_t n_blocks, const pga_topo_block_t *blocks, int64_t n_paths, const pga_topo_path_t *paths, int64_t n_nodes, const pga_topo_node_t *nodes,
+                               int64_t n_cut, const pga_apply_cut_t *cut, const pga_plan_interval_t *intervals, const pga_slice_res_t *slices,
+                               const pga_slice_member_t *members, pga_apply_out_t *out)
+{
+	if (!out) { set_err("pga_apply_merge: null output"); return -1; }
+	memset(out, 0, sizeof(*out));
+	try {
+		if (n_cut > 0) require_device();
+		pga::apply_merge_host(n_blocks, blocks, n_paths, paths, n_nodes, nodes, n_cut, cut, intervals, slices, members, out);
+		return 0;
+	} catch (std::exception &e) { pga_apply_free(out); set_err(e.what()); return -1; }
+}
+
 // ---------------------------------------------------------------- reweave's intervals and promises (pga_reweave.hip)
 namespace pga {
 struct RwResident { const uint16_t *nmask; uint64_t pos; };   // (pga_reweave_idx.h: where a block's "not ACGT" plane lies)

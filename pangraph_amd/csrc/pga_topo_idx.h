@@ -3,6 +3,7 @@
 // _nodes).  None of it uses a wave intrinsic -- the block scan goes through LDS and barriers -- so all of this compiles under hipcc and, with
 // dev/emu/hip_emu.h included first, under g++ -std=c++17 -DPGA_EMU (tests/emu/topo_emu.cpp runs it against a direct scalar construction).
 // The radix sort of the keys and the two scans over run heads are rocPRIM's (pga_topo.hip) and are not in here.
+// pga_apply_idx.h includes this header for the path lookup, the node hash and the splice: the kernels are static, one copy per translation unit.
 //
 // A POSITION is an index into nodes[] (path after path).  Its SUCCESSOR is the next position of its path, the path's first position behind
 // the last one of a circular path, or none; its EDGE is the pair (block, strand) -> (block, strand) of the two in conventional orientation,
@@ -103,7 +104,7 @@ __host__ __device__ inline uint64_t tp_node_id(uint64_t block_id, uint64_t path_
 }
 
 // ---------------------------------------------------------------- 1. edge keys and the slot counts, one thread per position
-__global__ __launch_bounds__(TP_THREADS) void k_topo_keys(TpDev V)
+static __global__ __launch_bounds__(TP_THREADS) void k_topo_keys(TpDev V)
 {
 	for (uint64_t i = (uint64_t)blockIdx.x * TP_THREADS + threadIdx.x; i < V.n_nodes; i += (uint64_t)gridDim.x * TP_THREADS) {
 		const uint32_t p = tp_path_of(V.paths, V.n_paths, i);
@@ -118,7 +119,7 @@ __global__ __launch_bounds__(TP_THREADS) void k_topo_keys(TpDev V)
 	}
 }
 // one thread per slot and per block: a slot named by no position or by two, a block whose positions do not sum to its depth
-__global__ __launch_bounds__(TP_THREADS) void k_topo_check(TpDev V)
+static __global__ __launch_bounds__(TP_THREADS) void k_topo_check(TpDev V)
 {
 	const uint64_t n = V.n_slots > V.n_blocks ? V.n_slots : V.n_blocks;
 	for (uint64_t x = (uint64_t)blockIdx.x * TP_THREADS + threadIdx.x; x < n; x += (uint64_t)gridDim.x * TP_THREADS) {
@@ -128,13 +129,13 @@ __global__ __launch_bounds__(TP_THREADS) void k_topo_check(TpDev V)
 }
 
 // ---------------------------------------------------------------- 2. runs of the sorted keys
-__global__ __launch_bounds__(TP_THREADS) void k_topo_heads(TpDev V)
+static __global__ __launch_bounds__(TP_THREADS) void k_topo_heads(TpDev V)
 {
 	for (uint64_t i = (uint64_t)blockIdx.x * TP_THREADS + threadIdx.x; i <= V.n_nodes; i += (uint64_t)gridDim.x * TP_THREADS)
 		V.head[i] = (i < V.n_nodes && V.skey[i] != TP_NOKEY && (i == 0 || V.skey[i] != V.skey[i - 1])) ? 1u : 0u;
 }
 // behind the scan of head[]: where every run starts; the first position without a key (or n_nodes) closes the last run
-__global__ __launch_bounds__(TP_THREADS) void k_topo_runs(TpDev V)
+static __global__ __launch_bounds__(TP_THREADS) void k_topo_runs(TpDev V)
 {
 	for (uint64_t i = (uint64_t)blockIdx.x * TP_THREADS + threadIdx.x; i <= V.n_nodes; i += (uint64_t)gridDim.x * TP_THREADS) {
 		const bool keyed = i < V.n_nodes && V.skey[i] != TP_NOKEY;
@@ -142,7 +143,7 @@ __global__ __launch_bounds__(TP_THREADS) void k_topo_runs(TpDev V)
 	}
 }
 // one thread per run: transitive when the two blocks differ and count == depth of both; every run's record when asked for
-__global__ __launch_bounds__(TP_THREADS) void k_topo_keep(TpDev V)
+static __global__ __launch_bounds__(TP_THREADS) void k_topo_keep(TpDev V)
 {
 	const uint64_t n_runs = V.head_off[V.n_nodes];
 	for (uint64_t r = (uint64_t)blockIdx.x * TP_THREADS + threadIdx.x; r <= V.n_nodes; r += (uint64_t)gridDim.x * TP_THREADS) {
@@ -155,7 +156,7 @@ __global__ __launch_bounds__(TP_THREADS) void k_topo_keep(TpDev V)
 		V.keep[r] = keep;
 	}
 }
-__global__ __launch_bounds__(TP_THREADS) void k_topo_compact(TpDev V)
+static __global__ __launch_bounds__(TP_THREADS) void k_topo_compact(TpDev V)
 {
 	const uint64_t n_runs = V.head_off[V.n_nodes];
 	for (uint64_t r = (uint64_t)blockIdx.x * TP_THREADS + threadIdx.x; r < n_runs; r += (uint64_t)gridDim.x * TP_THREADS)
@@ -170,7 +171,7 @@ __device__ inline bool tp_matched(const TpDev &V, uint32_t bx, uint32_t by, tp_u
 	r = V.choice[bx];
 	return r != TP_NONE && r == V.choice[by] && V.pick[r].key == key;
 }
-__global__ __launch_bounds__(TP_THREADS) void k_topo_pair(TpDev V)
+static __global__ __launch_bounds__(TP_THREADS) void k_topo_pair(TpDev V)
 {
 	for (uint64_t i = (uint64_t)blockIdx.x * TP_THREADS + threadIdx.x; i <= V.n_nodes; i += (uint64_t)gridDim.x * TP_THREADS) {
 		if (i == V.n_nodes) { V.cnt[i] = 0; continue; }
@@ -223,7 +224,7 @@ __device__ inline uint32_t tp_block_excl(uint32_t v, uint32_t *s, uint32_t &tota
 	__syncthreads();
 	return before;
 }
-__global__ __launch_bounds__(TP_THREADS) void k_topo_tile_sums(TpDev V)
+static __global__ __launch_bounds__(TP_THREADS) void k_topo_tile_sums(TpDev V)
 {
 	__shared__ uint32_t s[TP_THREADS];
 	for (uint32_t t = blockIdx.x; t < V.n_tiles; t += gridDim.x) {
@@ -235,7 +236,7 @@ __global__ __launch_bounds__(TP_THREADS) void k_topo_tile_sums(TpDev V)
 	}
 }
 // ONE workgroup: tile_off[t] = the nodes written by the tiles before t; tile_off[n_tiles] = all of them
-__global__ __launch_bounds__(TP_THREADS) void k_topo_tile_scan(TpDev V)
+static __global__ __launch_bounds__(TP_THREADS) void k_topo_tile_scan(TpDev V)
 {
 	__shared__ uint32_t s[TP_THREADS];
 	uint32_t run = 0;
@@ -248,7 +249,7 @@ __global__ __launch_bounds__(TP_THREADS) void k_topo_tile_scan(TpDev V)
 	}
 	if (threadIdx.x == 0) V.tile_off[V.n_tiles] = run;
 }
-__global__ __launch_bounds__(TP_THREADS) void k_topo_splice(TpDev V)
+static __global__ __launch_bounds__(TP_THREADS) void k_topo_splice(TpDev V)
 {
 	__shared__ uint32_t s[TP_THREADS];
 	for (uint32_t t = blockIdx.x; t < V.n_tiles; t += gridDim.x) {
@@ -268,7 +269,7 @@ __global__ __launch_bounds__(TP_THREADS) void k_topo_splice(TpDev V)
 	}
 }
 // a path's new node_off is the scanned value at its old node_off
-__global__ __launch_bounds__(TP_THREADS) void k_topo_paths(TpDev V)
+static __global__ __launch_bounds__(TP_THREADS) void k_topo_paths(TpDev V)
 {
 	for (uint64_t p = (uint64_t)blockIdx.x * TP_THREADS + threadIdx.x; p < V.n_paths; p += (uint64_t)gridDim.x * TP_THREADS) {
 		const pga_topo_path_t P = V.paths[p];

@@ -176,14 +176,59 @@ class ReweaveError(Exception):
     """the reference's reweave returns Err: a block fails refine_intervals (its status and interval are in the message)"""
 
 
-def reweave(graph, matches, thr_len, dll=None, plan=None, slicer=None):
+def _apply_update(g, p, bids, order, sliced_in, rows, update, dll):
+    """the graph update behind the slices as one pga_apply_merge call (update == "device") or a stand-in for it (a callable: blocks, paths,
+    nodes, cut, intervals, slices, members as lists -> what apply.ApplyOut.to_lists() gives), read back into the dicts -> halves"""
+    from . import apply as ap, topology as tp
+    args = tp.pack_graph(g, {b: sorted(blk["alignments"]) for b, blk in g["blocks"].items()})
+    at = {b: i for i, b in enumerate(sorted(g["blocks"]))}
+    cut = [(at[bids[b["block"]]], b["n_intervals"], b["first_interval"]) for b in p["blocks"]]
+    slices, members = [], []
+    for per_iv in rows:
+        for r in per_iv:
+            slices.append((len(members), len(r["kept"]), len(r["dropped"])))
+            members += [(m["member"], m["reverse"], m["pos"][0], m["pos"][1]) for m in r["kept"]]
+    if update == "device":
+        K = ap.pack_cut_lists(cut, p["intervals"], slices, members)
+        out = ap.apply_merge_raw(args, *K, dll=dll, keep=(args, K))
+        try:
+            res = out.to_lists(args[0])
+        finally:
+            out.free()
+    else:
+        res = update(*tp.unpack_lists(args), cut, p["intervals"], slices, members)
+    old = {n: g["nodes"].pop(n) for nids in order for n in nids}
+    halves, k = {}, 0
+    for b, blk, per_iv in zip(p["blocks"], sliced_in, rows):
+        for j, r in enumerate(per_iv):
+            iv = p["intervals"][b["first_interval"] + j]
+            new_block = {"consensus": blk["consensus"][iv["start"]:iv["end"]], "alignments": {}}
+            for m in r["kept"]:
+                nid, pos0, pos1, _, _, rev = res["new_nodes"][k]
+                new_block["alignments"][nid] = {"subs": list(m["subs"]), "dels": list(m["dels"]), "inss": list(m["inss"])}
+                g["nodes"][nid] = {"block_id": iv["new_block_id"], "path_id": old[res["old_node"][k]]["path_id"], "strand": "-" if rev else "+", "position": (pos0, pos1)}
+                k += 1
+            if iv["aligned"]:
+                halves[(iv["new_block_id"], bool(iv["is_anchor"]))] = new_block
+            else:
+                g["blocks"][iv["new_block_id"]] = new_block
+    for b in p["blocks"]:
+        del g["blocks"][bids[b["block"]]]
+    for pid, off, n, _ in res["paths"]:
+        g["paths"][pid]["nodes"] = [x[0] for x in res["nodes"][off:off + n]]
+    return halves
+
+
+def reweave(graph, matches, thr_len, dll=None, plan=None, slicer=None, update=None):
     """reweave (reweave.rs:408-453) on a graph in the shape of simplify.normalize() (changed in place and returned).
     matches: [{"qry": block id, "ref": block id, "qry_start", "qry_end", "ref_start", "ref_end", "reverse", "cigar"}].
     plan -> pga_slice_blocks -> node ids (simplify.node_id) -> GraphUpdate (reweave.rs:359-401, 445-450; a reverse old node gets its new
     nodes in reverse order).  -> (graph, promises): a promise is {"new_block_id", "anchor": block, "append": block, "reverse", "cigar"}
     with block = {"consensus", "alignments": {new node id: edit}} -- what promise.solve_promises takes per promise is (anchor consensus,
     append consensus, reverse, [(len, kind)], the append block's edits in node id order).
-    plan / slicer stand in for the device calls (groups, matches, thr_len -> plan_merge's result; blocks -> slice_blocks' result)."""
+    plan / slicer stand in for the device calls (groups, matches, thr_len -> plan_merge's result; blocks -> slice_blocks' result).
+    update: None -- the loop over the dicts below; "device" -- one pga_apply_merge call (pangraph_amd/apply.py) on topology.pack_graph's arrays,
+    read back into the same dicts; a callable stands in for that call."""
     from . import simplify, slice as sl
     g = graph
     bids = sorted({m["qry"] for m in matches} | {m["ref"] for m in matches})
@@ -204,6 +249,10 @@ def reweave(graph, matches, thr_len, dll=None, plan=None, slicer=None):
                           "nodes": [(o["position"][0], o["position"][1], g["paths"][o["path_id"]]["tot_len"], o["strand"] == "-", g["paths"][o["path_id"]]["circular"]) for o in old],
                           "intervals": p["slice_intervals"][b["first_interval"]:b["first_interval"] + b["n_intervals"]]})
     rows = (slicer or (lambda bl: sl.slice_blocks(bl, dll=dll)))(sliced_in)
+    if update is not None:
+        halves = _apply_update(g, p, bids, order, sliced_in, rows, update, dll)
+        return g, [{"new_block_id": q["new_block_id"], "anchor": halves[(q["new_block_id"], True)], "append": halves[(q["new_block_id"], False)],
+                    "reverse": bool(q["reverse"]), "cigar": list(q["cigar"])} for q in p["promises"]]
     halves, n_new = {}, {}
     for b, nids, blk, per_iv in zip(p["blocks"], order, sliced_in, rows):
         for n in nids:
