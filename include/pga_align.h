@@ -771,6 +771,61 @@ int pga_apply_merge(int64_t n_blocks, const pga_topo_block_t *blocks, int64_t n_
                     int64_t n_cut, const pga_apply_cut_t *cut, const pga_plan_interval_t *intervals,
                     const pga_slice_res_t *slices, const pga_slice_member_t *members, pga_apply_out_t *out);
 void pga_apply_free(pga_apply_out_t *out);
+
+/* ---- simplify: the removal of the paths that are not focal (commands/simplify/simplify_run.rs:23-38 over Pangraph::remove_path,
+ * pangraph/pangraph.rs:110-132) ----
+ * pga_remove_paths is remove_path for every path p with keep[p] == 0, in any order (the result does not depend on it), on the flat graph of
+ * pga_plan_simplify AND the block arrays of pga_merge_blocks at once.  Input, only read:
+ *   blocks, paths, nodes   the three arrays of pga_plan_simplify, with its rules.
+ *   rc_blocks, members, subs, dels, inss, ins_seq   the arrays of pga_reconsensus / pga_merge_blocks / pga_reconstruct in the same block index
+ *                      order: rc_blocks[i] is blocks[i], n_members == depth for an alive block and 0 for a dead one.  The member of a node is
+ *                      global member first_member[block] + member, first_member the running sum of n_members.
+ *   keep[n_paths]      non-zero: the path stays.
+ *   flags              PGA_REMOVE_COMPACT_LETTERS, see below.
+ * Output (freed with pga_remove_free), all exact integers:
+ *   blocks[n_blocks]   block indices do not move.  A block keeps block_id; depth = its kept members; a block left without a member has
+ *                      alive = 0, depth = 0, cons_len = 0, as pga_plan_simplify leaves a dead block, and so has a block that was dead.  (An
+ *                      alive block given with depth 0 stays as it is; the reference never holds one.)  n_dead_blocks counts alive == 0.
+ *   rc_blocks[n_blocks]   consensus and cons_len as given (no consensus letter moves), n_members = the kept members (0 for a dead block).
+ *   paths, nodes       the kept paths in input order, node_off the running sum again; their nodes with id, strand, positions and order
+ *                      unchanged, block unchanged, member = the node's rank among the kept members of its block.
+ *   members, subs, dels, inss   the kept members in input order (so in their relative order inside every block), their three lists copied
+ *                      in that order into dense arrays.
+ *   member_map[m]      the place in members[] after of input member m, -1 for a removed one.  path_map[p]: the same for paths.
+ *   insertion letters  without PGA_REMOVE_COMPACT_LETTERS seq_off stays as given, ins_seq is not read and may be NULL, out->ins_seq is
+ *                      NULL and the caller's buffer goes on serving (the arrangement of pga_detach_unaligned).  With it the letters of
+ *                      the kept insertions are gathered in output order into out->ins_seq (n_ins_letters of them) and seq_off becomes the
+ *                      running sum of len; the seq_off given may be in any order and may overlap.
+ *   (n_blocks, blocks, n_paths, paths, n_nodes, nodes) are the first six arguments of pga_plan_simplify and the graph of pga_apply_merge;
+ *   (n_blocks, rc_blocks, members, subs, dels, inss, ins_seq -- the caller's or out->ins_seq) the first seven of pga_merge_blocks,
+ *   pga_reconstruct and the two exports: pointers only.
+ * keep all non-zero gives the input, copied; keep all zero the empty graph: 0 paths, 0 nodes, every block dead.  n_paths == 0 returns
+ * without a device call.
+ * Malformed input fails the call (-1, message in pga_last_error(), out zeroed).  Before anything is launched: every refusal pga_plan_simplify
+ * makes on the host for the three graph arrays (alive block ids not strictly ascending, path ids not ascending, a node naming a block out of
+ * range or a dead block, member >= depth, n_nodes of the paths not summing to the node count or node_off not the running sum, 2^31 or more
+ * nodes, blocks, paths or members), a NULL array with a non-zero count, NULL keep with n_paths > 0, an unknown flag,
+ * rc_blocks[i].n_members != blocks[i].depth or a dead block with members, edit counts that overflow 2^63, members without a single path.
+ * On the device, before any index derived from it is used: a (block, member) slot named by no node or by two, nodes of a block not summing
+ * to its depth; with PGA_REMOVE_COMPACT_LETTERS, before a letter is read: NULL ins_seq while a kept insertion has letters, seq_off + len >
+ * ins_seq_len of a kept insertion.  The path table after is made on the host (O(paths)).  The call waits for the device twice, three times
+ * with the flag: the checks and totals, the letter total, the output. */
+#define PGA_REMOVE_COMPACT_LETTERS 1u
+typedef struct {
+	int64_t n_blocks, n_paths, n_nodes, n_members, n_dead_blocks;      /* n_blocks == the input's: block indices do not move */
+	uint64_t n_subs, n_dels, n_inss, n_ins_letters;
+	pga_topo_block_t *blocks; pga_topo_path_t *paths; pga_topo_node_t *nodes;            /* the graph after, pga_plan_simplify's layout */
+	pga_rc_block_t *rc_blocks; pga_rc_member_t *members; pga_sub_t *subs; pga_del_t *dels; pga_ins_t *inss; char *ins_seq;   /* the block arrays after */
+	int64_t *member_map;     /* [input members] place in members[] after, or -1 */
+	int32_t *path_map;       /* [input paths]   place in paths[] after, or -1 */
+} pga_remove_out_t;
+int pga_remove_paths(int64_t n_blocks, const pga_topo_block_t *blocks, int64_t n_paths, const pga_topo_path_t *paths, int64_t n_nodes, const pga_topo_node_t *nodes,
+                     const pga_rc_block_t *rc_blocks, const pga_rc_member_t *members, const pga_sub_t *subs, const pga_del_t *dels, const pga_ins_t *inss,
+                     const char *ins_seq, uint64_t ins_seq_len, const uint8_t *keep /* [n_paths], non-zero: the path stays */, uint32_t flags, pga_remove_out_t *out);
+void pga_remove_free(pga_remove_out_t *out);
+/* Measurement only: the stream's clock over the last pga_remove_paths call of the calling thread that reached the device, in ms:
+ * ms[0] the uploads, ms[1] the kernels with the waits between them, ms[2] the downloads. */
+void pga_remove_last_ms(double *ms /* 3 */);
 int pga_stats_version(void);   /* == PGA_STATS_VERSION of the header the library was built with */
 /* Measurement only (no reference interface behind it): the kern_ms sums of pga_stats_t count overlapping launches on different streams
  * and batches several times.  Between pga_busy_begin() and pga_busy_end() every event-bracketed launch of the process leaves its interval

@@ -1233,6 +1233,34 @@ extern "C" int pga_apply_merge(int64_t n_blocks, const pga_topo_block_t *blocks,
 	} catch (std::exception &e) { pga_apply_free(out); set_err(e.what()); return -1; }
 }
 
+// ---------------------------------------------------------------- simplify's path removal (pga_remove.hip)
+namespace pga {
+void remove_paths_host(int64_t n_blocks, const pga_topo_block_t *blocks, int64_t n_paths, const pga_topo_path_t *paths, int64_t n_nodes, const pga_topo_node_t *nodes,
+                       const pga_rc_block_t *rc_blocks, const pga_rc_member_t *members, const pga_sub_t *subs, const pga_del_t *dels, const pga_ins_t *inss,
+                       const char *ins_seq, uint64_t ins_seq_len, const uint8_t *keep, uint32_t flags, pga_remove_out_t *out);
+void remove_last_ms(double *ms);
+}
+extern "C" void pga_remove_free(pga_remove_out_t *o)
+{
+	if (!o) return;
+	free(o->blocks); free(o->paths); free(o->nodes); free(o->rc_blocks); free(o->members); free(o->subs); free(o->dels); free(o->inss); free(o->ins_seq);
+	free(o->member_map); free(o->path_map);
+	memset(o, 0, sizeof(*o));
+}
+extern "C" void pga_remove_last_ms(double *ms) { if (ms) pga::remove_last_ms(ms); }
+extern "C" int pga_remove_paths(int64_t n_blocks, const pga_topo_block_t *blocks, int64_t n_paths, const pga_topo_path_t *paths, int64_t n_nodes, const pga_topo_node_t *nodes,
+                                const pga_rc_block_t *rc_blocks, const pga_rc_member_t *members, const pga_sub_t *subs, const pga_del_t *dels, const pga_ins_t *inss,
+                                const char *ins_seq, uint64_t ins_seq_len, const uint8_t *keep, uint32_t flags, pga_remove_out_t *out)
+{
+	if (!out) { set_err("pga_remove_paths: null output"); return -1; }
+	memset(out, 0, sizeof(*out));
+	try {
+		if (n_paths > 0) require_device();
+		pga::remove_paths_host(n_blocks, blocks, n_paths, paths, n_nodes, nodes, rc_blocks, members, subs, dels, inss, ins_seq, ins_seq_len, keep, flags, out);
+		return 0;
+	} catch (std::exception &e) { pga_remove_free(out); set_err(e.what()); return -1; }
+}
+
 // ---------------------------------------------------------------- reweave's intervals and promises (pga_reweave.hip)
 namespace pga {
 struct RwResident { const uint16_t *nmask; uint64_t pos; };   // (pga_reweave_idx.h: where a block's "not ACGT" plane lies)

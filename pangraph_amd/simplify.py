@@ -2,7 +2,8 @@
 (Pangraph::remove_path, pangraph/pangraph.rs:110-132) and transitive edges are merged until none is left (circularize/circularize.rs:11-76,
 circularize/merge_blocks.rs:15-234).  The graph bookkeeping, O(nodes), is done here; the block concatenations -- consensus letters and edit
 lists -- are `pga_merge_blocks` (include/pga_align.h), one call per ROUND of disjoint edges.  ctypes only; the HIP library does the work.
-With simplify(topology="device") the graph bookkeeping of a round is one `pga_plan_simplify` call as well (topology.py).
+With simplify(topology="device") the graph bookkeeping of a round is one `pga_plan_simplify` call as well (topology.py); with
+simplify(paths="device") the removal of the paths is one `pga_remove_paths` call (remove.py) whose arrays the first round reads by pointer.
 
 The reference merges `find_transitive_edges(graph).first()` of a HashMap iteration until none is left: its order is undefined, and for chains
 the orientation and the id of the final block depend on it.  The DEFINED order here: in every round the transitive edges are sorted by
@@ -252,10 +253,12 @@ def choose_round(transitive):
 
 class _DeviceRounds:
     """one pga_merge_blocks call per round.  A round whose blocks all lie in the previous round's output passes that output's arrays on
-    as they are (pointers only); otherwise the blocks the round names are packed from the graph."""
+    as they are (pointers only); otherwise the blocks the round names are packed from the graph.  `prev` / `prev_at` stand for a round
+    before the first: an object with graph_args() (the seven block arguments) and free(), and the index of every block id in its arrays
+    (remove.Removed: the output of pga_remove_paths)."""
 
-    def __init__(self, dll):
-        self.dll, self.prev, self.prev_at, self.zero_copy = dll, None, {}, []
+    def __init__(self, dll, prev=None, prev_at=None):
+        self.dll, self.prev, self.prev_at, self.zero_copy = dll, prev, dict(prev_at or {}), []
 
     def __call__(self, g, order, jobs):
         named = []
@@ -281,18 +284,20 @@ class _DeviceRounds:
             self.prev = None
 
 
-def _simplify_planned(g, order, dll, schedule, merge, trace, topology):
+def _simplify_planned(g, order, dll, schedule, merge, trace, topology, first=None):
     """simplify()'s loop with the path side in pga_plan_simplify (topology.py): the graph is packed once, every round is one call whose
     output arrays are the next round's input, `round` and `partner` feed the block merge as they come, and the dicts are rebuilt once at
-    the end.  Inside the loop only blocks are touched on the host: O(merged members), no walk over paths or nodes."""
+    the end.  Inside the loop only blocks are touched on the host: O(merged members), no walk over paths or nodes.
+    first (a remove.Removed): the graph is not packed at all -- the planner starts on the arrays pga_remove_paths left, whose block indices
+    are those of the loaded graph (first.bids), dead blocks included."""
     from . import topology as tp
-    args = tp.pack_graph(g, order)
+    args = tp.pack_graph(g, order) if first is None else first.args
     planner = tp.DevicePlanner(args, dll) if topology == "device" else tp.StandInPlanner(args, topology)
-    bids = sorted(g["blocks"])
+    bids = sorted(g["blocks"]) if first is None else first.bids
     index = {b: i for i, b in enumerate(bids)}
     strand = lambda rev: "-" if rev else "+"
-    blocks = {"blocks": {b: {"consensus": g["blocks"][b]["consensus"], "alignments": [g["blocks"][b]["alignments"][n] for n in order[b]]} for b in bids}}
-    slots = {b: range(len(order[b])) for b in bids}                               # (a block's members are named by their slot from here on)
+    blocks = {"blocks": {b: {"consensus": g["blocks"][b]["consensus"], "alignments": [g["blocks"][b]["alignments"][n] for n in order[b]]} for b in sorted(g["blocks"])}}
+    slots = {b: range(len(order[b])) for b in blocks["blocks"]}                   # (a block's members are named by their slot from here on)
     device, rounds, lists = None, [], []
     try:
         while True:
@@ -325,7 +330,7 @@ def _simplify_planned(g, order, dll, schedule, merge, trace, topology):
                 out = merge([{"consensus": blocks["blocks"][b]["consensus"], "members": blocks["blocks"][b]["alignments"]} for b in named],
                             [dict(j, left=at[j["left"]], right=at[j["right"]]) for j in jobs])
             else:
-                device = device or _DeviceRounds(dll)
+                device = device or (_DeviceRounds(dll) if first is None or first.out is None else _DeviceRounds(dll, first, first.at))
                 out = device(blocks, slots, jobs)
             for j, r in zip(jobs, out):
                 if r["status"] != 0:
@@ -353,21 +358,47 @@ def _simplify_planned(g, order, dll, schedule, merge, trace, topology):
     return out
 
 
-def simplify(graph, focal_names, dll=None, schedule=None, merge=None, trace=None, topology=None):
+def simplify(graph, focal_names, dll=None, schedule=None, merge=None, trace=None, topology=None, paths=None):
     """graph: a parsed pangraph JSON; focal_names: the paths to keep.  -> the simplified graph in the shape of normalize().
     schedule: explicit first rounds, [[edge, ...], ...] with edge = ((block id, strand), (block id, strand)); every round's edges must be
     transitive and share no block; behind the last of them the defined order goes on.  merge: stands in for the device call (blocks, edges as merge_blocks takes them -> its result).
     trace: a dict that receives "rounds" (the rounds taken) and "zero_copy" (per device round: its input was the previous output).
     topology: None -- the graph level is the host functions of this module; "device" -- it is pga_plan_simplify, one call per round
     (topology.py), or a callable standing in for that call (blocks, paths, nodes, sched, flags as lists -> what PlanOut.to_lists() gives);
-    trace then also receives "transitive", the transitive edges of every round taken."""
+    trace then also receives "transitive", the transitive edges of every round taken.
+    paths: None -- the paths that are not focal are removed by remove_path, one after the other; "device" -- the loaded graph is packed once
+    and they are removed by one pga_remove_paths call (remove.py), whose arrays the first round reads by pointer: the planner of
+    topology="device" its graph, the first pga_merge_blocks call its blocks (trace["zero_copy"][0] is True); or a callable standing in for
+    that call (see remove.removed_graph)."""
     g = normalize(graph)
     focal = set(focal_names)
+    if paths is not None:
+        from . import remove as rm
+        first = rm.removed_graph(g, focal, paths, dll)
+        try:
+            return _simplify_removed(first, dll, schedule, merge, trace, topology)
+        finally:
+            first.close()
     for pid in [pid for pid in sorted(g["paths"]) if g["paths"][pid]["name"] not in focal]:
         remove_path(g, pid)
     order = {b: sorted(blk["alignments"]) for b, blk in g["blocks"].items()}      # the member order of every block in the arrays
     if topology is not None:
         return _simplify_planned(g, order, dll, schedule, merge, trace, topology)
+    return _simplify_rounds(g, order, dll, schedule, merge, trace)
+
+
+def _simplify_removed(first, dll, schedule, merge, trace, topology):
+    """simplify() behind pga_remove_paths: the same two loops, started on the arrays of that call.  The members of a block keep their
+    relative order, so the member order of the arrays is still the node id order."""
+    g = first.g
+    order = {b: sorted(blk["alignments"]) for b, blk in g["blocks"].items()}
+    if topology is not None:
+        return _simplify_planned(g, order, dll, schedule, merge, trace, topology, first)
+    return _simplify_rounds(g, order, dll, schedule, merge, trace, first)
+
+
+def _simplify_rounds(g, order, dll, schedule, merge, trace, first=None):
+    """simplify()'s loop with the graph level on the host"""
     device = None
     rounds = []
     try:
@@ -397,7 +428,7 @@ def simplify(graph, focal_names, dll=None, schedule=None, merge=None, trace=None
                 res = merge([{"consensus": g["blocks"][b]["consensus"], "members": [g["blocks"][b]["alignments"][n] for n in order[b]]} for b in named],
                             [dict(j, left=at[j["left"]], right=at[j["right"]]) for j in jobs])
             else:
-                device = device or _DeviceRounds(dll)
+                device = device or (_DeviceRounds(dll) if first is None or first.out is None else _DeviceRounds(dll, first, first.at))
                 res = device(g, order, jobs)
             for j, (e, new), r in zip(jobs, plans, res):
                 if r["status"] != 0:
