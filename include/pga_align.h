@@ -826,6 +826,65 @@ void pga_remove_free(pga_remove_out_t *out);
 /* Measurement only: the stream's clock over the last pga_remove_paths call of the calling thread that reached the device, in ms:
  * ms[0] the uploads, ms[1] the kernels with the waits between them, ms[2] the downloads. */
 void pga_remove_last_ms(double *ms /* 3 */);
+
+/* ---- export gfa (io/gfa.rs:79-279 gfa_write / convert_pangraph_to_gfa, Edge of circularize/circularize_utils.rs:46-102) ----
+ * pga_export_gfa writes, for the flat graph of pga_plan_simplify (blocks, paths, nodes: its rules, only read) and GfaWriteParams, the bytes
+ * gfa_write_str gives, and returns the tables behind them.  By the reference:
+ *   segments   (gfa.rs:264-279 graph_to_gfa_segment) one candidate per alive block: length = cons_len, depth = blocks[].depth, duplicated =
+ *              two of its nodes lie on one path (PangraphBlock::is_duplicated), on the unfiltered graph.
+ *   filter     (gfa.rs:239-262 gfa_filter_path) a node stays when its block has min_len <= length <= max_len and min_depth <= depth <=
+ *              max_depth, bounds inclusive (absent bounds: 0 and UINT64_MAX), and with no_duplicated is not duplicated.
+ *   paths      (gfa.rs:176-183, :218-237) in input order (ascending path_id), `circular` kept as it was; a path with no node left is
+ *              dropped, one that was empty before too.
+ *   emitted segments   (gfa.rs:185-190) the blocks some kept node names, in ascending block index (ascending id).
+ *   links      (gfa.rs:201-216 gfa_paths_to_links) on the FILTERED paths: every two consecutive kept nodes, and the last followed by the
+ *              first on a circular path (one kept node: the self link (n, n); a linear path has no wrap link).  An edge equals its
+ *              inversion ((b2, !s2), (b1, !s1)) (circularize_utils.rs:51-56, :82-86); it is emitted in conventional_orientation
+ *              (circularize_utils.rs:65-71: as it stands when b1 < b2, or b1 == b2 and s1 forward, else inverted), sorted by (b1, b2, s1,
+ *              s2) with forward = 0 (gfa.rs:108-114), one record per distinct edge with its count: the keys of pga_plan_simplify.
+ *   text       (gfa.rs:79-137), exactly:  "H\tVN:Z:1.0\n";  if any segment "# blocks\n" and per segment
+ *              "S\t{id}\t{consensus or *}\tRC:i:{depth*length}\tLN:i:{length}" ["\tTP:Z:duplicated"] "\n";  if any link "# edges\n" and per
+ *              link "L\t{id1}\t{+|-}\t{id2}\t{+|-}\t*\tRC:i:{count}\n";  if any path "# paths\n" and per path
+ *              "P\t{name}\t{id}{+|-},{id}{+|-}...\t*" ["\tTP:Z:circular"] "\n".  Ids are block_id in decimal (u64, up to 20 digits), RC of
+ *              a segment is the 64-bit product.
+ * Input besides the graph:
+ *   cons[n_blocks]     per block cons_len letters; read only with include_sequences, and only for emitted blocks.
+ *   names, name_len    per input path its name as raw bytes (no NUL needed); read only for emitted paths.
+ *   p                  the parameters; flags: PGA_GFA_STEPS also returns steps[].
+ * Output (freed with pga_gfa_free): segments[] (block: index into blocks; byte_off: of its S line in the file), links[] (block indices),
+ * paths[] (path: index into the input paths; its steps are steps[step_off .. step_off + n_steps); byte_off: of its P line), steps[] (with
+ * PGA_GFA_STEPS: the kept nodes path after path, 8 bytes each; otherwise NULL), n_steps (always), n_bytes: the length of the file.
+ * sink == NULL is verdict mode: the tables and n_bytes, no text byte is produced.  sink != NULL: called on the calling thread with
+ * consecutive pieces of the file in file order, each at most PGA_EXPORT_TILE_KB KB (default 16384; a multiple of 4, read at every call);
+ * their concatenation is the file, n_bytes long.  A sink that returns non-zero stops the export: what is in flight is drained, no further
+ * call is made and the entry returns -1 ("sink stopped the export").  The whole text is never held on the device or the host: the library
+ * keeps the tables, one or two tiles and its cached pinned blocks.  Consensus letters and path names never go to the device: the kernel
+ * leaves their byte ranges of a tile unwritten and the host copies them from the caller's buffers into the pinned tile (piecewise where
+ * one is longer than a tile), O(segments + paths) per call plus the bytes copied.
+ * Malformed input fails the call (-1, message in pga_last_error(), out zeroed).  Before anything is launched: every refusal
+ * pga_plan_simplify makes on the host for the three arrays, p == NULL, min > max in either pair, an unknown flag, include_sequences with
+ * cons == NULL.  On the device, before any index derived from it is used: a (block, member) slot named by no node or by two, nodes of a
+ * block not summing to its depth.  Behind the first wait, before a text byte is made: a NULL consensus of an emitted block of non-zero
+ * length (include_sequences), names == NULL or a NULL name with a non-zero length for an emitted path, a file of 2^63 bytes or more (held
+ * against an upper bound that exceeds the true length by less than 2^41).  n_paths == 0 or n_nodes == 0 gives the header line only,
+ * without a device call. */
+typedef struct { uint64_t min_len, max_len, min_depth, max_depth; int32_t no_duplicated, include_sequences; } pga_gfa_params_t;
+typedef struct { uint32_t block, depth, cons_len; int32_t duplicated; uint64_t byte_off; } pga_gfa_segment_t;  /* byte_off: of its S line in the file */
+typedef struct { uint32_t path, n_steps; uint64_t step_off, byte_off; } pga_gfa_path_t;                         /* path: index into the input paths */
+typedef struct { uint32_t block; int32_t reverse; } pga_gfa_step_t;
+typedef struct { int64_t n_segments, n_links, n_paths, n_steps; uint64_t n_bytes;
+                 pga_gfa_segment_t *segments; pga_topo_edge_t *links; pga_gfa_path_t *paths; pga_gfa_step_t *steps; } pga_gfa_out_t;
+typedef int (*pga_gfa_sink_t)(void *ctx, const char *bytes, int64_t n);
+#define PGA_GFA_STEPS 1u      /* also return steps[] (8 bytes per kept node); otherwise NULL */
+int  pga_export_gfa(int64_t n_blocks, const pga_topo_block_t *blocks, int64_t n_paths, const pga_topo_path_t *paths, int64_t n_nodes, const pga_topo_node_t *nodes,
+                    const char *const *cons /* per block, cons_len letters; read only with include_sequences */,
+                    const char *const *names, const uint32_t *name_len /* per path, raw bytes, no NUL needed */,
+                    const pga_gfa_params_t *p, uint32_t flags, pga_gfa_out_t *out, pga_gfa_sink_t sink, void *ctx);
+void pga_gfa_free(pga_gfa_out_t *out);
+/* Measurement only: the last pga_export_gfa call of the calling thread that reached the device, in ms: ms[0] the stream's clock from the
+ * first upload to the tables (the table kernels and their waits), ms[1] the union of the tile kernels on the stream's clock, ms[2] the
+ * host's copies of consensus letters and names into the tiles (host clock), ms[3] the time spent inside the sink (host clock). */
+void pga_gfa_last_ms(double *ms /* 4 */);
 int pga_stats_version(void);   /* == PGA_STATS_VERSION of the header the library was built with */
 /* Measurement only (no reference interface behind it): the kern_ms sums of pga_stats_t count overlapping launches on different streams
  * and batches several times.  Between pga_busy_begin() and pga_busy_end() every event-bracketed launch of the process leaves its interval

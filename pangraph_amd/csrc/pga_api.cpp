@@ -1261,6 +1261,33 @@ extern "C" int pga_remove_paths(int64_t n_blocks, const pga_topo_block_t *blocks
 	} catch (std::exception &e) { pga_remove_free(out); set_err(e.what()); return -1; }
 }
 
+// ---------------------------------------------------------------- export gfa (pga_gfa.hip)
+namespace pga {
+void export_gfa_host(int64_t n_blocks, const pga_topo_block_t *blocks, int64_t n_paths, const pga_topo_path_t *paths, int64_t n_nodes, const pga_topo_node_t *nodes,
+                     const char *const *cons, const char *const *names, const uint32_t *name_len, const pga_gfa_params_t *p, uint32_t flags, pga_gfa_out_t *out,
+                     pga_gfa_sink_t sink, void *ctx);
+void gfa_last_ms(double *ms);
+}
+extern "C" void pga_gfa_free(pga_gfa_out_t *o)
+{
+	if (!o) return;
+	free(o->segments); free(o->links); free(o->paths); free(o->steps);
+	memset(o, 0, sizeof(*o));
+}
+extern "C" void pga_gfa_last_ms(double *ms) { if (ms) pga::gfa_last_ms(ms); }
+extern "C" int pga_export_gfa(int64_t n_blocks, const pga_topo_block_t *blocks, int64_t n_paths, const pga_topo_path_t *paths, int64_t n_nodes, const pga_topo_node_t *nodes,
+                              const char *const *cons, const char *const *names, const uint32_t *name_len, const pga_gfa_params_t *p, uint32_t flags, pga_gfa_out_t *out,
+                              pga_gfa_sink_t sink, void *ctx)
+{
+	if (!out) { set_err("pga_export_gfa: null output"); return -1; }
+	memset(out, 0, sizeof(*out));
+	try {
+		if (n_paths > 0 && n_nodes > 0) require_device();
+		pga::export_gfa_host(n_blocks, blocks, n_paths, paths, n_nodes, nodes, cons, names, name_len, p, flags, out, sink, ctx);
+		return 0;
+	} catch (std::exception &e) { pga_gfa_free(out); set_err(e.what()); return -1; }
+}
+
 // ---------------------------------------------------------------- reweave's intervals and promises (pga_reweave.hip)
 namespace pga {
 struct RwResident { const uint16_t *nmask; uint64_t pos; };   // (pga_reweave_idx.h: where a block's "not ACGT" plane lies)
