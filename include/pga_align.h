@@ -885,6 +885,54 @@ void pga_gfa_free(pga_gfa_out_t *out);
  * first upload to the tables (the table kernels and their waits), ms[1] the union of the tile kernels on the stream's clock, ms[2] the
  * host's copies of consensus letters and names into the tiles (host clock), ms[3] the time spent inside the sink (host clock). */
 void pga_gfa_last_ms(double *ms /* 4 */);
+
+/* ---- the pangraph JSON (serde_json::to_writer_pretty of Pangraph: build_run.rs:78 and simplify_run.rs:20 write it with JsonPretty(true)) ----
+ * pga_export_json writes, for the flat graph of pga_plan_simplify (blocks, paths, nodes: its rules, only read) and the block arrays of
+ * pga_reconsensus, the bytes of the reference's graph file, and returns where its parts start.  The text, exactly:
+ *   layout     two-space indent, ": " behind a key, every entry of a non-empty map or list on a line of its own, an empty list "[]", an empty
+ *              map "{}", no trailing newline.  The top level holds "paths", "blocks", "nodes" in that order; map keys are the ids as decimal
+ *              strings.  Fields: path id, nodes, tot_len, circular, name, desc; block id, consensus, alignments; alignment subs, dels, inss;
+ *              Sub pos, alt; Del pos, len; Ins pos, seq; node id, block_id, path_id, strand ("+" / "-"), position [pos0, pos1].
+ *   orders     the reference's BTreeMaps: paths by ascending path_id (input order), alive blocks by ascending block_id (index order), the
+ *              "nodes" map by ascending node_id, the alignments of a block by ascending node_id of the node that names the slot, whatever
+ *              order the slots are in.  Both come from a device sort of the node ids, by id and then stably by block.  The edits of a
+ *              member stay in input order, the nodes of a path in path order.
+ * Input besides the graph:
+ *   cons[n_blocks]     per block cons_len letters, copied verbatim: the caller's contract, as in pga_export_gfa, is that they need no
+ *                      escaping (no '"', no '\', no byte below 0x20).  Read for alive blocks only.
+ *   members, subs, dels, inss, ins_seq   one pga_rc_member_t per slot, block after block (blocks[b].depth entries in member order, dead
+ *                      blocks none), the three lists member after member; ins_seq_len: the letters at ins_seq.  seq_off may be in any order
+ *                      and insertions may share letters.  alt and every insertion letter must be printable ASCII other than '"' and '\'.
+ *   tot_len, names, name_len, descs, desc_len   per path; names[i] == NULL / descs[i] == NULL is JSON null, otherwise raw bytes (no NUL
+ *                      needed) that are escaped by serde's rules: \" \\ \b \f \n \r \t, other bytes below 0x20 as \u00xx with lower-case
+ *                      hex, everything else verbatim (0x7f and bytes >= 0x80 too).
+ *   flags              none defined: must be 0.
+ * Output (freed with pga_json_free): n_bytes the length of the file; section_off[3] the offsets of the opening quotes of "paths", "blocks"
+ * and "nodes"; path_off[n_paths] / block_off[n_blocks] the offset of the opening quote of every path's / block's key (UINT64_MAX for a
+ * dead block); node_order[n_nodes] the positions in ascending node_id, the order of the "nodes" map.
+ * sink == NULL is verdict mode: the tables and n_bytes, no text byte is produced.  sink != NULL: as pga_export_gfa, consecutive pieces of
+ * at most PGA_EXPORT_TILE_KB KB on the calling thread; a sink that returns non-zero stops the export (-1, "sink stopped the export").  The
+ * whole text is never held on the device or the host.  The device writes all structure, all numbers, alt and the insertion letters (ins_seq
+ * is uploaded once); consensus letters, names and descriptions never go to the device: the kernel leaves their byte ranges unwritten and
+ * the host copies them (names and descriptions escaped) into the pinned tile, O(blocks + paths) per call plus the bytes copied.
+ * Malformed input fails the call (-1, message in pga_last_error(), out zeroed).  Before anything is launched: every refusal
+ * pga_plan_simplify makes on the host for the three arrays, an unknown flag, NULL members with a slot, a NULL edit list with a non-zero
+ * count, NULL ins_seq with a non-zero ins_seq_len, NULL tot_len, names, name_len, descs or desc_len with n_paths > 0, a NULL consensus of an alive block
+ * of non-zero length.  On the device, before any index derived from it is used: a (block, member) slot named by no node or by two, nodes
+ * of a block not summing to its depth, two nodes with one node_id, an alt or an insertion letter outside 0x20..0x7e or equal to '"' or
+ * '\', an insertion whose seq_off + len runs past ins_seq_len.  A file of 2^63 bytes or more is refused (held against an upper bound that
+ * exceeds the true length by less than 2^9 bytes per path, block, node and edit).  n_blocks == n_paths == n_nodes == 0 gives the three
+ * empty maps without a device call. */
+typedef struct { uint64_t n_bytes, section_off[3]; int64_t n_paths, n_blocks, n_nodes; uint64_t *path_off, *block_off; uint32_t *node_order; } pga_json_out_t;
+int  pga_export_json(int64_t n_blocks, const pga_topo_block_t *blocks, int64_t n_paths, const pga_topo_path_t *paths, int64_t n_nodes, const pga_topo_node_t *nodes,
+                     const char *const *cons /* per block, cons_len letters that need no escaping */,
+                     const pga_rc_member_t *members, const pga_sub_t *subs, const pga_del_t *dels, const pga_ins_t *inss, const char *ins_seq, uint64_t ins_seq_len,
+                     const uint64_t *tot_len, const char *const *names, const uint32_t *name_len, const char *const *descs, const uint32_t *desc_len /* per path; NULL: null */,
+                     uint32_t flags, pga_json_out_t *out, pga_gfa_sink_t sink, void *ctx);
+void pga_json_free(pga_json_out_t *out);
+/* Measurement only, as pga_gfa_last_ms: ms[0] from the first upload to the layout, ms[1] the union of the tile kernels, ms[2] the host's
+ * copies of consensus letters, names and descriptions into the tiles, ms[3] the time spent inside the sink. */
+void pga_json_last_ms(double *ms /* 4 */);
 int pga_stats_version(void);   /* == PGA_STATS_VERSION of the header the library was built with */
 /* Measurement only (no reference interface behind it): the kern_ms sums of pga_stats_t count overlapping launches on different streams
  * and batches several times.  Between pga_busy_begin() and pga_busy_end() every event-bracketed launch of the process leaves its interval

@@ -1288,6 +1288,36 @@ extern "C" int pga_export_gfa(int64_t n_blocks, const pga_topo_block_t *blocks, 
 	} catch (std::exception &e) { pga_gfa_free(out); set_err(e.what()); return -1; }
 }
 
+// ---------------------------------------------------------------- the pangraph JSON (pga_json.hip)
+namespace pga {
+void export_json_host(int64_t n_blocks, const pga_topo_block_t *blocks, int64_t n_paths, const pga_topo_path_t *paths, int64_t n_nodes, const pga_topo_node_t *nodes,
+                      const char *const *cons, const pga_rc_member_t *members, const pga_sub_t *subs, const pga_del_t *dels, const pga_ins_t *inss, const char *ins_seq,
+                      uint64_t n_ins_seq, const uint64_t *tot_len, const char *const *names, const uint32_t *name_len, const char *const *descs, const uint32_t *desc_len,
+                      uint32_t flags, pga_json_out_t *out, pga_gfa_sink_t sink, void *ctx);
+void json_last_ms(double *ms);
+}
+extern "C" void pga_json_free(pga_json_out_t *o)
+{
+	if (!o) return;
+	free(o->path_off); free(o->block_off); free(o->node_order);
+	memset(o, 0, sizeof(*o));
+}
+extern "C" void pga_json_last_ms(double *ms) { if (ms) pga::json_last_ms(ms); }
+extern "C" int pga_export_json(int64_t n_blocks, const pga_topo_block_t *blocks, int64_t n_paths, const pga_topo_path_t *paths, int64_t n_nodes, const pga_topo_node_t *nodes,
+                               const char *const *cons, const pga_rc_member_t *members, const pga_sub_t *subs, const pga_del_t *dels, const pga_ins_t *inss, const char *ins_seq,
+                               uint64_t ins_seq_len, const uint64_t *tot_len, const char *const *names, const uint32_t *name_len, const char *const *descs,
+                               const uint32_t *desc_len, uint32_t flags, pga_json_out_t *out, pga_gfa_sink_t sink, void *ctx)
+{
+	if (!out) { set_err("pga_export_json: null output"); return -1; }
+	memset(out, 0, sizeof(*out));
+	try {
+		if (n_blocks > 0 || n_paths > 0 || n_nodes > 0) require_device();
+		pga::export_json_host(n_blocks, blocks, n_paths, paths, n_nodes, nodes, cons, members, subs, dels, inss, ins_seq, ins_seq_len, tot_len, names, name_len, descs, desc_len,
+		                      flags, out, sink, ctx);
+		return 0;
+	} catch (std::exception &e) { pga_json_free(out); set_err(e.what()); return -1; }
+}
+
 // ---------------------------------------------------------------- reweave's intervals and promises (pga_reweave.hip)
 namespace pga {
 struct RwResident { const uint16_t *nmask; uint64_t pos; };   // (pga_reweave_idx.h: where a block's "not ACGT" plane lies)
