@@ -182,6 +182,38 @@ int pga_stage_post_identity(int32_t n, const uint8_t *const *q, const int32_t *q
  * thresholds, the band w of the global pass (negative: none), its zdropped flag and score, and its operation list: 1 = the walk may be skipped.
  * A pass whose band does not cover its whole matrix is never skipped.  Host arithmetic, no device. */
 int pga_stage_zdrop_impossible(int q, int e, int q2, int e2, int a, int zdrop, int zdrop_inv, int w, int zdropped, int score, int32_t n_cigar, const uint32_t *cigar);
+/* The region planner (pga_plan.hip: what mm_align1 decides before its first DP call) on explicit inputs, through the production plan_regions.
+ * The three records mirror PlanParams, PlanOut and PlanItem of pga_plan.h field by field.
+ * Sequences are base codes 0..4, packed one behind the other in call order as the resident store is packed (sequence 0 at position 0, the tail
+ * padded with code 4).  Sequences [base, n_seq) are the group: an anchor's target id t names sequence base + t.  Query j of the call is sequence
+ * q_seq[j] (an index into the whole call, inside the group); its anchors are anchors_xy[2 anchor_off[j] .. 2 anchor_off[j+1]), two uint64 per
+ * anchor (x = strand<<63 | target<<32 | target position, y = flags | span<<32 | query position on the aligned strand).  Region r is
+ * regions[3r ..] = query index, as, cnt.  Every field of params is taken as given; the PGA_PLAN_G_MAX variable is not read, and g_max above 4096
+ * is refused.
+ * out[r] is the region's record; its items are (*items)[item_off[r] .. item_off[r+1]) (item_off has n_regions + 1 entries; a region whose status
+ * is not 0 has none; *items is freed with pga_free()).  anchors_xy comes back as the kernels left it, flags included.
+ * The kernels validate nothing, so the tap refuses by name, without a launch: a region outside its query's anchors; a cnt below 0 (cnt = 0 is
+ * valid: status 3); an anchor whose target id is outside the group; an anchor whose position, or position minus k/2, falls outside its sequence;
+ * a chain that is not strictly ascending on one target, strand and both coordinates. */
+typedef struct {
+	int32_t k, bw, bw_long, max_gap, min_cnt, min_chain_score, min_ksw_len, a, q, e, no_end_flt, probe_m_max;
+	int32_t g_max, pad;
+	int64_t max_sw_mat;
+} pga_region_params_t;
+typedef struct {
+	int32_t status;                                          /* 0 ok, 2 more than g_max long gaps, 3 empty chain */
+	int32_t rid, rev;
+	int32_t r_rs, r_re, r_qs, r_qe, r_mlen, r_blen;
+	int32_t as1, cnt1, rs, qs, rs0, qs0, re0, qe0, T_re, T_qe;
+	uint32_t n_items; int32_t n_long_gaps;
+} pga_region_out_t;
+typedef struct {
+	int32_t kind, i, rs, qs, re, qe, bw1, m, i_prev;         /* kind 0: a run of bw1 answered segments with m mismatches; 1 / 2: a segment for the DP */
+	int32_t pad[3];
+} pga_region_item_t;
+int pga_stage_plan(int32_t n_seq, const uint8_t *const *seq, const int32_t *seq_len, int32_t base, int32_t n_q, const int32_t *q_seq,
+                   const uint64_t *anchor_off, uint64_t *anchors_xy, int32_t n_regions, const int32_t *regions, const pga_region_params_t *params,
+                   pga_region_out_t *out, pga_region_item_t **items, uint64_t *item_off);
 /* radix_sort_128x (ksort.h:101-151, misc.c:155-159), the exact replay incl. the arrangement of equal keys: sorts every array
  * [seg_off[s], seg_off[s+1]) of the n_seg arrays in xy (two uint64 per record: x = key, y = payload) in place */
 int pga_stage_sort(int32_t n_seg, const uint64_t *seg_off, uint64_t *xy);

@@ -12,6 +12,7 @@
 #include "pga_pipeline.h"
 #include "pga_dp.h"
 #include "pga_post.h"
+#include "pga_plan.h"
 #include "../../include/pga_align.h"
 #include <atomic>
 #include <chrono>
@@ -833,6 +834,11 @@ struct PostStore {
 			q_off[(size_t)i] = buf.size(); buf.insert(buf.end(), q[i], q[i] + qlen[i]);
 			t_off[(size_t)i] = buf.size(); buf.insert(buf.end(), t[i], t[i] + tlen[i]);
 		}
+		pack(buf);
+	}
+	// base codes 0..4, the first at position 0 of the store; the tail is padded with code 4
+	void pack(std::vector<uint8_t> &buf)
+	{
 		buf.resize((buf.size() + 15) / 16 * 16 + 128, 4);
 		std::vector<uint32_t> pk(buf.size() / 16, 0u); std::vector<uint16_t> nm(buf.size() / 16, 0);
 		for (size_t i = 0; i < buf.size(); ++i) { const uint8_t c = buf[i]; if (c > 3) nm[i >> 4] |= (uint16_t)(1u << (i & 15)); else pk[i >> 4] |= (uint32_t)c << (2 * (i & 15)); }
@@ -947,6 +953,73 @@ extern "C" int pga_stage_zdrop_impossible(int q, int e, int q2, int e2, int a, i
 	DpRes R; memset(&R, 0, sizeof(R));
 	R.zdropped = zdropped, R.score = score, R.n_cigar = n_cigar;
 	return zdrop_impossible(mo, R, cigar, w) ? 1 : 0;
+}
+
+// ---- the region planner (pga_plan.hip) on explicit inputs: the production plan_regions, unchanged.  Its kernels validate nothing, so this does ----
+static_assert(sizeof(pga_region_params_t) == sizeof(PlanParams) && sizeof(pga_region_out_t) == sizeof(PlanOut) && sizeof(pga_region_item_t) == sizeof(PlanItem),
+              "pga_stage_plan hands the planner's records in and out as they lie");
+extern "C" int pga_stage_plan(int32_t n_seq, const uint8_t *const *seq, const int32_t *seq_len, int32_t base, int32_t n_q, const int32_t *q_seq,
+                              const uint64_t *anchor_off, uint64_t *anchors_xy, int32_t n_regions, const int32_t *regions, const pga_region_params_t *params,
+                              pga_region_out_t *out, pga_region_item_t **items, uint64_t *item_off)
+{
+	if (items) *items = nullptr;
+	try {
+		require_device();
+		const std::string who = "pga_stage_plan: ";
+		if (n_seq < 0 || n_q < 0 || n_regions < 0 || !params || !items || !item_off || (n_seq && (!seq || !seq_len)) || (n_q && (!q_seq || !anchor_off)) || (n_regions && (!regions || !out)))
+			throw std::runtime_error(who + "null argument");
+		PlanParams P; memcpy(&P, params, sizeof(P));
+		if (P.g_max < 0 || P.g_max > 4096) throw std::runtime_error(who + "g_max outside [0, 4096]");
+		if (P.k < 1 || P.min_cnt < 0) throw std::runtime_error(who + "k below 1 or min_cnt below 0");
+		if (base < 0 || base > n_seq) throw std::runtime_error(who + "the group's first sequence is outside the store");
+		for (int i = 0; i < n_seq; ++i) if (seq_len[i] < 0) throw std::runtime_error(who + "negative sequence length");
+		const int half_k = P.k >> 1;
+		const uint64_t n_anchors = n_q ? anchor_off[n_q] : 0;
+		if (n_anchors && !anchors_xy) throw std::runtime_error(who + "null argument");
+		for (int j = 0; j < n_q; ++j) {
+			if (anchor_off[j + 1] < anchor_off[j] || anchor_off[j + 1] - anchor_off[j] > (uint64_t)INT32_MAX) throw std::runtime_error(who + "anchor_off descends");
+			if (q_seq[j] < base || q_seq[j] >= n_seq) throw std::runtime_error(who + "query " + std::to_string(j) + " is outside the group");
+			const int32_t qlen = seq_len[q_seq[j]];
+			for (uint64_t i = anchor_off[j]; i < anchor_off[j + 1]; ++i) {
+				const uint64_t x = anchors_xy[2 * i], y = anchors_xy[2 * i + 1];
+				const int64_t rid = (int64_t)(x << 1 >> 33);
+				const std::string what = "anchor " + std::to_string(i - anchor_off[j]) + " of query " + std::to_string(j);
+				if (rid >= n_seq - base) throw std::runtime_error(who + what + ": target id outside the group");
+				const int32_t tpos = (int32_t)x, qpos = (int32_t)y, tlen = seq_len[base + rid];
+				if (tpos - half_k < 0 || tpos >= tlen || qpos - half_k < 0 || qpos >= qlen) throw std::runtime_error(who + what + ": position outside its sequence");
+			}
+		}
+		std::vector<PlanIn> in((size_t)n_regions);
+		for (int r = 0; r < n_regions; ++r) {
+			const int32_t j = regions[3 * r], as = regions[3 * r + 1], cnt = regions[3 * r + 2];
+			const std::string what = "region " + std::to_string(r);
+			if (j < 0 || j >= n_q) throw std::runtime_error(who + what + ": query index outside the call");
+			if (cnt < 0) throw std::runtime_error(who + what + ": cnt below 0");
+			const int64_t n_a = (int64_t)(anchor_off[j + 1] - anchor_off[j]);
+			if (as < 0 || (int64_t)as + cnt > n_a) throw std::runtime_error(who + what + ": outside its query's anchors");
+			const uint64_t *a = anchors_xy + 2 * anchor_off[j];
+			for (int i = as + 1; i < as + cnt; ++i)
+				if (a[2 * i] >> 32 != a[2 * (i - 1)] >> 32 || (int32_t)a[2 * i] <= (int32_t)a[2 * (i - 1)] || (int32_t)a[2 * i + 1] <= (int32_t)a[2 * (i - 1) + 1])
+					throw std::runtime_error(who + what + ": non-monotone chain");
+			PlanIn &R = in[(size_t)r]; memset(&R, 0, sizeof(R));
+			R.a_off = anchor_off[j]; R.n_a = (int32_t)n_a; R.as = as; R.cnt = cnt; R.qlen = seq_len[q_seq[j]]; R.qid = q_seq[j]; R.base = base;
+		}
+		for (int r = 0; r <= n_regions; ++r) item_off[r] = 0;
+		// the store: every sequence of the call, one behind the other
+		PostStore S; std::vector<uint8_t> buf; std::vector<uint64_t> off((size_t)n_seq); std::vector<uint32_t> len((size_t)n_seq);
+		for (int i = 0; i < n_seq; ++i) { off[(size_t)i] = buf.size(); len[(size_t)i] = (uint32_t)seq_len[i]; buf.insert(buf.end(), seq[i], seq[i] + seq_len[i]); }
+		S.pack(buf);
+		DBuf<uint64_t> d_off; d_off.upload(off, 0); DBuf<uint32_t> d_len; d_len.upload(len, 0);
+		DBuf<u128> d_a; d_a.upload((const u128*)anchors_xy, (size_t)n_anchors, 0);
+		std::vector<PlanOut> po; std::vector<PlanItem> pi;
+		plan_regions(in, d_a.p, S.view(), d_off.p, d_len.p, P, po, pi, 0);
+		if (n_anchors) { PGA_HIP(hipMemcpyAsync(anchors_xy, d_a.p, (size_t)n_anchors * sizeof(u128), hipMemcpyDeviceToHost, 0)); PGA_HIP(sync_stream(0)); }
+		memcpy(out, po.data(), (size_t)n_regions * sizeof(PlanOut));
+		for (int r = 0; r < n_regions; ++r) item_off[r + 1] = item_off[r] + (po[(size_t)r].status == 0 ? po[(size_t)r].n_items : 0);
+		if (item_off[n_regions] != pi.size()) throw std::runtime_error(who + "the item list does not match the regions' counts");
+		*items = (pga_region_item_t*)dup_out(pi);
+		return 0;
+	} catch (std::exception &e) { set_err(e.what()); return -1; }
 }
 
 extern "C" void pga_stage_dp_routes(int64_t by_class[14], int64_t handed_back[2]) { dp_routes_take(by_class, handed_back); }
