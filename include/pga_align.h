@@ -859,6 +859,77 @@ void pga_remove_free(pga_remove_out_t *out);
  * ms[0] the uploads, ms[1] the kernels with the waits between them, ms[2] the downloads. */
 void pga_remove_last_ms(double *ms /* 3 */);
 
+/* ---- self-merge: the block arrays behind a round (solve_promise's tail, reweave.rs:88-93 alignment_insert; the insertion of the merged
+ * blocks, graph_merging.rs:156-165; the blocks split_block leaves, reweave.rs:359-401) ----
+ * pga_assemble_blocks executes the gather list of pga_apply_merge: it builds the consensus pointers, member counts, three edit lists and
+ * insertion letters of every block of the graph that pga_apply_merge returns, from what the calls before it returned, as it stands.  With it
+ * pga_plan_merge -> pga_slice_blocks -> pga_apply_merge / pga_solve_promises -> pga_assemble_blocks -> pga_detach_unaligned -> pga_reconsensus
+ * (or pga_reconstruct, pga_plan_simplify + pga_merge_blocks, the exports, the next round) is one chain by pointer.  Input, only read:
+ *   rc_blocks, members, subs, dels, inss, ins_seq   the block arrays of the graph BEFORE in the arrangement of pga_remove_paths: rc_blocks[i] is
+ *                      blocks[i] of the graph given to pga_apply_merge, n_members == depth for an alive block and 0 for a dead one.
+ *   cut, intervals     as given to pga_apply_merge.  promises: plan.promises.  slice: the pga_slice_blocks output.
+ *   res, p_subs, p_dels, p_inss, p_ins_seq   the pga_solve_promises output of the call whose promise p is plan.promises[p] with the kept members
+ *                      of slice promises[p].append_interval, in that order: their results are res[first_res[p] ..), first_res the running sum
+ *                      of those n_kept over the promises in order.
+ *   applied            the pga_apply_merge output.
+ * Everything else is derived: the slice count is the sum of cut[].n_intervals, the slice members and their edit totals come from the last
+ * slice and its last member, the totals of the promise results from the last res[] entry.
+ * Output (freed with pga_assemble_free), all exact integers.  Default mode: block i is applied->blocks[i], n_members == depth, from one of
+ *   a survivor         (block_map[old] == i) the caller's consensus pointer, members and lists, copied in order;
+ *   an unaligned slice (new_blocks[].kind == 0) consensus = the cut block's pointer + interval.start, end - start letters (no consensus letter
+ *                      is copied, the rule of pga_slice_blocks); the members named by member_src in slot order with their sliced edits
+ *                      (slice->subs / dels / inss);
+ *   a merged block     (kind == 1) the consensus of the anchor interval; slot s is slice.members[member_src[member_off + s]]: a member of the
+ *                      anchor slice (interval_a) brings its sliced edits, one of the append slice (interval_b) those of its res[] entry
+ *                      (counts and offsets into p_subs / p_dels / p_inss).
+ *   insertion letters  always gathered in output order into out->ins_seq (n_ins_letters of them), seq_off the running sum of len.  Sources:
+ *                      the caller's ins_seq (survivors, sliced edits) and p_ins_seq (promise results); a source seq_off may be in any order
+ *                      and may overlap.  One buffer, which the next call takes by pointer.
+ *   who[m]             node id and strand of member m after, scattered from applied->nodes (who[first_member[block] + member] = (node_id,
+ *                      reverse)): the who argument of pga_detach_unaligned, and the member-to-node map pga_reconstruct, pga_export_json and
+ *                      pga_remove_paths assume.
+ *   origin[m]          >= 0: the global member before (a survivor's); -(1 + k): slice.members[k].
+ * PGA_ASSEMBLE_MERGED_ONLY: only the kind == 1 blocks, in new_blocks[] order, with the same members, lists, letters, who and origin: what
+ * pga_detach_unaligned -> pga_reconsensus take after a round.
+ * (out->n_blocks, blocks, members, subs, dels, inss, ins_seq) are the first seven arguments of pga_detach_unaligned, pga_reconsensus,
+ * pga_reconstruct, pga_merge_blocks, pga_remove_paths (rc side) and the exports: pointers only.
+ * n_cut == 0 (applied is all zero then): the default mode returns the input copied with compacted letters, who NULL (no node moved, the
+ * caller's map stands), origin the identity; merged-only returns empty lists.  n_blocks == 0: no device call.
+ * Malformed input fails the call (-1, message in pga_last_error(), out zeroed).  Before anything is launched: a NULL array with a non-zero
+ * count, an unknown flag, cut / intervals / slice tables that pga_apply_merge refuses on the host (a cut block out of range or named twice,
+ * n_intervals == 0, first_interval not the running sum, intervals not ascending and disjoint, member_off not the running sum of n_kept) or
+ * an interval beyond its block's consensus, applied->n_new_nodes, n_blocks, block_map or new_blocks[] inconsistent with the tables (a block
+ * after named twice or by nobody, depth != the kept members of its slices, member_off not the running sum), a kind == 1 block whose
+ * interval_b is no promise's append_interval, a promise whose anchor_interval / append_interval disagree with new_blocks[], a survivor whose
+ * rc_blocks[].n_members != depth after, a block neither cut nor mapped that has members, 2^31 or more members or blocks, edit totals that
+ * overflow 2^63.  On the device, before any index derived from it is used: a member_src entry outside its block's two slices or used twice,
+ * a res[] entry of a used append member with status != 0 (the reference's solve_promise returns Err and the merge fails; the message names
+ * the promise and the member), a source offset + count beyond its list, seq_off + len beyond ins_seq_len / p_ins_seq_len (before a letter
+ * is read; a NULL buffer has length 0), a node of applied->nodes naming a slot twice, outside its block or leaving one unfilled.
+ * The call waits for the device three times: the checks and list totals, the letter checks and total, the output. */
+#define PGA_ASSEMBLE_MERGED_ONLY 1u
+#define PGA_ASSEMBLE_TILE 1024   /* positions per workgroup of the scans and of the element copies */
+typedef struct {
+	int64_t n_blocks, n_members; uint64_t n_subs, n_dels, n_inss, n_ins_letters;
+	pga_rc_block_t *blocks; pga_rc_member_t *members; pga_sub_t *subs; pga_del_t *dels; pga_ins_t *inss; char *ins_seq;
+	pga_detach_member_t *who;   /* per member after: node id and strand */
+	int64_t *origin;            /* per member after: >= 0 the global member before (a survivor); -(1 + k): slice.members[k] */
+} pga_assemble_out_t;
+int  pga_assemble_blocks(
+	int64_t n_blocks, const pga_rc_block_t *rc_blocks, const pga_rc_member_t *members, const pga_sub_t *subs, const pga_del_t *dels,
+	const pga_ins_t *inss, const char *ins_seq, uint64_t ins_seq_len,                          /* the graph BEFORE, pga_remove_paths' arrangement */
+	int64_t n_cut, const pga_apply_cut_t *cut, const pga_plan_interval_t *intervals,
+	int64_t n_promises, const pga_plan_promise_t *promises,                                    /* plan output, as it stands */
+	const pga_slice_out_t *slice,                                                              /* pga_slice_blocks output, as it stands */
+	const pga_mapvar_res_t *res, const pga_sub_t *p_subs, const pga_del_t *p_dels, const pga_ins_t *p_inss,
+	const char *p_ins_seq, uint64_t p_ins_seq_len,                                             /* pga_solve_promises output, as it stands */
+	const pga_apply_out_t *applied,                                                            /* pga_apply_merge output, as it stands */
+	uint32_t flags, pga_assemble_out_t *out);
+void pga_assemble_free(pga_assemble_out_t *out);
+/* Measurement only: the stream's clock over the last pga_assemble_blocks call of the calling thread that reached the device, in ms:
+ * ms[0] the uploads, ms[1] the kernels with the waits between them, ms[2] the downloads. */
+void pga_assemble_last_ms(double *ms /* 3: uploads, kernels with their waits, downloads */);
+
 /* ---- export gfa (io/gfa.rs:79-279 gfa_write / convert_pangraph_to_gfa, Edge of circularize/circularize_utils.rs:46-102) ----
  * pga_export_gfa writes, for the flat graph of pga_plan_simplify (blocks, paths, nodes: its rules, only read) and GfaWriteParams, the bytes
  * gfa_write_str gives, and returns the tables behind them.  By the reference:

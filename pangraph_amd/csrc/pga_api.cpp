@@ -1334,6 +1334,38 @@ extern "C" int pga_remove_paths(int64_t n_blocks, const pga_topo_block_t *blocks
 	} catch (std::exception &e) { pga_remove_free(out); set_err(e.what()); return -1; }
 }
 
+// ---------------------------------------------------------------- the block arrays behind a merge round (pga_assemble.hip)
+namespace pga {
+void assemble_blocks_host(int64_t n_blocks, const pga_rc_block_t *rc_blocks, const pga_rc_member_t *members, const pga_sub_t *subs, const pga_del_t *dels,
+                          const pga_ins_t *inss, const char *ins_seq, uint64_t ins_seq_len, int64_t n_cut, const pga_apply_cut_t *cut, const pga_plan_interval_t *intervals,
+                          int64_t n_promises, const pga_plan_promise_t *promises, const pga_slice_out_t *slice, const pga_mapvar_res_t *res, const pga_sub_t *p_subs,
+                          const pga_del_t *p_dels, const pga_ins_t *p_inss, const char *p_ins_seq, uint64_t p_ins_seq_len, const pga_apply_out_t *applied, uint32_t flags,
+                          pga_assemble_out_t *out);
+void assemble_last_ms(double *ms);
+}
+extern "C" void pga_assemble_free(pga_assemble_out_t *o)
+{
+	if (!o) return;
+	free(o->blocks); free(o->members); free(o->subs); free(o->dels); free(o->inss); free(o->ins_seq); free(o->who); free(o->origin);
+	memset(o, 0, sizeof(*o));
+}
+extern "C" void pga_assemble_last_ms(double *ms) { if (ms) pga::assemble_last_ms(ms); }
+extern "C" int pga_assemble_blocks(int64_t n_blocks, const pga_rc_block_t *rc_blocks, const pga_rc_member_t *members, const pga_sub_t *subs, const pga_del_t *dels,
+                                   const pga_ins_t *inss, const char *ins_seq, uint64_t ins_seq_len, int64_t n_cut, const pga_apply_cut_t *cut,
+                                   const pga_plan_interval_t *intervals, int64_t n_promises, const pga_plan_promise_t *promises, const pga_slice_out_t *slice,
+                                   const pga_mapvar_res_t *res, const pga_sub_t *p_subs, const pga_del_t *p_dels, const pga_ins_t *p_inss, const char *p_ins_seq,
+                                   uint64_t p_ins_seq_len, const pga_apply_out_t *applied, uint32_t flags, pga_assemble_out_t *out)
+{
+	if (!out) { set_err("pga_assemble_blocks: null output"); return -1; }
+	memset(out, 0, sizeof(*out));
+	try {
+		if (n_blocks > 0 && (n_cut > 0 || !(flags & PGA_ASSEMBLE_MERGED_ONLY))) require_device();
+		pga::assemble_blocks_host(n_blocks, rc_blocks, members, subs, dels, inss, ins_seq, ins_seq_len, n_cut, cut, intervals, n_promises, promises, slice, res, p_subs, p_dels,
+		                          p_inss, p_ins_seq, p_ins_seq_len, applied, flags, out);
+		return 0;
+	} catch (std::exception &e) { pga_assemble_free(out); set_err(e.what()); return -1; }
+}
+
 // ---------------------------------------------------------------- export gfa (pga_gfa.hip)
 namespace pga {
 void export_gfa_host(int64_t n_blocks, const pga_topo_block_t *blocks, int64_t n_paths, const pga_topo_path_t *paths, int64_t n_nodes, const pga_topo_node_t *nodes,
