@@ -157,6 +157,34 @@ int pga_stage_chain_anchors(int32_t n_seq, const uint64_t *q_aoff, const uint64_
  * reloads of the backtrack's walks */
 #define PGA_N_CHAIN_ROUTES 15
 void pga_stage_chain_routes(int64_t out[PGA_N_CHAIN_ROUTES]);
+/* build_index_ex, mm_idx_cal_max_occ + mm_mapopt_update, and mm_seed_mz_flt / mm_collect_matches / collect_seed_hits (index.c:186-270, options.c:66-80,
+ * seed.c:5-131, map.c:78-100,168-204) of a batch of n_grp all-vs-all groups on minimizers given as they are.  Sequence i has length lens[i] and name
+ * names[i]; group g holds the sequences [grp_off[g], grp_off[g+1]); the minimizers of sequence i are mz_xy[2 mz_off[i] .. 2 mz_off[i+1]) in
+ * mm_sketch's layout (x = hash << 8 | k, y = i << 32 | pos << 1 | strand).  own (or NULL): own[i] == 0 leaves query i unmapped while its
+ * minimizers stay targets.  params: mid_occ > 0 is taken as given, 0 derives it per group from mid_occ_frac and the two clamps.
+ * mode 0: every query's anchors in the reference's arrangement of equal keys (the replay of radix_sort_128x); 1: in stable order, as a batch
+ * leaves them, with q_tie[q] != 0 where query q holds equal keys (q_tie is zeroed in mode 0).
+ * Caller-allocated outputs: mid_occ [n_grp]; state [mz_off[n_seq]]: per minimizer 0 dropped by the query filter, 1 seed used, 2 seed filtered,
+ * plus 4 for a tandem seed; rep_len, q_tie [n_seq]; anchor_off [n_seq + 1].  *anchors_xy (two uint64 per anchor, query q's at
+ * anchor_off[q] .. anchor_off[q+1]) is freed with pga_free().
+ * The kernels validate nothing, so the tap refuses by name, without a launch: a minimizer whose rid is not its sequence; positions that do not
+ * ascend inside a sequence; a position outside [k - 1, len); a low byte of x other than k; a hash of 2k bits or more; duplicate names inside a
+ * group; groups that are not contiguous; k or w outside the supported range; a flag bit other than the four skip_seed reads. */
+typedef struct {
+	int64_t flag;
+	int32_t mid_occ, min_mid_occ, max_mid_occ, max_max_occ, occ_dist, w, k;
+	float mid_occ_frac, q_occ_frac;
+	int32_t pad;
+} pga_seed_params_t;
+int pga_stage_seed(int32_t n_seq, const uint32_t *lens, const char *const *names, int32_t n_grp, const int64_t *grp_off, const uint64_t *mz_off,
+                   const uint64_t *mz_xy, const uint8_t *own, const pga_seed_params_t *params, int mode,
+                   int32_t *mid_occ, uint8_t *state, int32_t *rep_len, uint64_t *anchor_off, uint64_t **anchors_xy, uint32_t *q_tie);
+/* which branch of the stages in front of chaining answered, in every call of the process since the last call of this function (copied out and
+ * zeroed): 0-3 sketch launches of k_sketch_tiles8<19>, k_sketch_tiles8<10>, k_sketch_tiles and k_sketch_serial (two per call: it counts, then
+ * writes); 4 retries of the sketch's staging slabs; 5 index builds by one sort, 6 by two; 7 mid_occ batches answered by the histograms, 8 by the
+ * sort; 9 queries sent through the sort replay (counted in calls of pga_stage_seed only).  Host-side counters: no launch or copy is added. */
+#define PGA_N_FRONT_ROUTES 10
+void pga_stage_front_routes(int64_t out[PGA_N_FRONT_ROUTES]);
 /* The post-DP kernels (pga_post.hip) on explicit inputs.  Layout contract of the three device taps: sequences are base codes 0..4; they are packed
  * as the resident store is packed and laid out as pga_stage_extd2 lays them out -- request order, the FULL forward query of request i directly
  * followed by its FULL target, the first base at position 0 of the store with no padding in front (request 0 has q_off == 0, the only place

@@ -142,6 +142,7 @@ static void require_device()
 	}
 }
 
+static void check_kw(int k, int w) { if (k > 28 || k < 1 || w < 1 || w > 255) throw std::runtime_error("pga: k must be in [1,28] and w in [1,255]"); }
 static void check_supported(const mm_mapopt_t &o, int k, int w)
 {
 	if (o.flag & (MM_F_SPLICE | MM_F_SR | MM_F_QSTRAND | MM_F_HEAP_SORT | MM_F_EQX))
@@ -153,7 +154,7 @@ static void check_supported(const mm_mapopt_t &o, int k, int w)
 	// (the reference tests behind its exchange of the two pairs, ksw2_extd2_sse.c:78 and :100: against the cheaper one, and returns an empty record for every problem)
 	const int qe_min = std::min(o.q + o.e, o.q2 + o.e2);
 	if (o.b > 2 * qe_min) throw std::runtime_error("pga: mismatch penalty b = " + std::to_string(o.b) + " is larger than 2*(q+e) = " + std::to_string(2 * qe_min) + " of the cheaper gap pair: that disables the reference DP");
-	if (k > 28 || k < 1 || w < 1 || w > 255) throw std::runtime_error("pga: k must be in [1,28] and w in [1,255]");
+	check_kw(k, w);
 	if (o.sdust_thres > 0) throw std::runtime_error("pga: SDUST masking is not implemented");
 	// the inversion test (ksw_ll_i16, align.c:845-855) runs over windows of up to max_gap bases and the device kernel holds 10 240: refused
 	// here, by name, instead of in the middle of a batch (every asm preset has max_gap = 5 000 or 10 000)
@@ -332,7 +333,7 @@ static bool seqs_same_bases(const SeqSet &S, int qid, const char *seq, int l_seq
 	int k = 0;
 	for (int i = 0; i < l_seq && k < 64; i += step, ++k) {
 		const char c = seq[i] & 0xdf; uint8_t code = c == 'A' ? 0 : c == 'C' ? 1 : c == 'G' ? 2 : (c == 'T' || c == 'U') ? 3 : 4;
-		if ((uint8_t)seq[i] < 0x40) code = 4;
+		if ((uint8_t)seq[i] < 0x40) code = (uint8_t)seq[i] < 4 ? (uint8_t)seq[i] : 4;      // (bytes 0..3 are bases too: sketch.c:10)
 		if (code != h[k]) return false;
 	}
 	return true;
@@ -778,6 +779,105 @@ extern "C" int pga_stage_chain(const pga_params_t *params, int32_t n, const char
 		return 0;
 	} catch (std::exception &e) { set_err(e.what()); return -1; }
 }
+
+// The minimizer-level tap: build_index_ex, index_cal_max_occ / group_mid_occ and seed_all as a batch runs them, on minimizers given as they are --
+// occurrence counts chosen by a test, not produced by sketching.  seed_all reads lengths, names and group tables of the sequence set, never a base:
+// the sequences handed over are all N.  The kernels validate nothing, so whatever they would index out of bounds on is refused here, by name.
+static_assert(sizeof(pga_seed_params_t) == 48, "pga_stage_seed takes the record as it lies");
+extern "C" int pga_stage_seed(int32_t n_seq, const uint32_t *lens, const char *const *names, int32_t n_grp, const int64_t *grp_off, const uint64_t *mz_off,
+                              const uint64_t *mz_xy, const uint8_t *own, const pga_seed_params_t *params, int mode,
+                              int32_t *mid_occ, uint8_t *state, int32_t *rep_len, uint64_t *anchor_off, uint64_t **anchors_xy, uint32_t *q_tie)
+{
+	try {
+		const std::string who = "pga_stage_seed: ";
+		if (n_seq <= 0 || n_grp <= 0 || !lens || !names || !grp_off || !mz_off || !params || !mid_occ || !rep_len || !anchor_off || !anchors_xy || !q_tie)
+			throw std::runtime_error(who + "null argument");
+		if (mode != 0 && mode != 1) throw std::runtime_error(who + "mode is 0 (the reference's arrangement of equal keys) or 1 (stable order, as a batch leaves it)");
+		const pga_seed_params_t &P = *params;
+		const int k = P.k, w = P.w;
+		check_kw(k, w);
+		if (P.flag & ~(int64_t)(MM_F_NO_DIAG | MM_F_NO_DUAL | MM_F_FOR_ONLY | MM_F_REV_ONLY))
+			throw std::runtime_error(who + "flag holds bits other than MM_F_NO_DIAG, MM_F_NO_DUAL, MM_F_FOR_ONLY and MM_F_REV_ONLY");
+		if (grp_off[0] != 0 || grp_off[n_grp] != n_seq) throw std::runtime_error(who + "groups are not contiguous: grp_off must run from 0 to n_seq");
+		for (int g = 0; g < n_grp; ++g) if (grp_off[g + 1] < grp_off[g]) throw std::runtime_error(who + "groups are not contiguous: grp_off descends at group " + std::to_string(g));
+		if (mz_off[0] != 0) throw std::runtime_error(who + "mz_off[0] != 0");
+		for (int i = 0; i < n_seq; ++i) if (mz_off[i + 1] < mz_off[i]) throw std::runtime_error(who + "mz_off descends");
+		const uint64_t n_mz = mz_off[n_seq];
+		if (n_mz && (!mz_xy || !state)) throw std::runtime_error(who + "null argument");
+		uint32_t max_len = 0;
+		for (int i = 0; i < n_seq; ++i) {
+			if (!names[i]) throw std::runtime_error(who + "sequence " + std::to_string(i) + " has no name");
+			max_len = std::max(max_len, lens[i]);
+			int64_t last = -1;
+			for (uint64_t j = mz_off[i]; j < mz_off[i + 1]; ++j) {
+				const uint64_t x = mz_xy[2 * j], y = mz_xy[2 * j + 1];
+				const std::string at = "minimizer " + std::to_string(j - mz_off[i]) + " of sequence " + std::to_string(i);
+				if ((y >> 32) != (uint64_t)i) throw std::runtime_error(who + at + " carries rid " + std::to_string(y >> 32));
+				const int64_t pos = (uint32_t)y >> 1;
+				if (pos <= last) throw std::runtime_error(who + at + ": positions do not ascend");
+				if (pos < k - 1 || pos >= (int64_t)lens[i]) throw std::runtime_error(who + at + ": position " + std::to_string(pos) + " is outside [k - 1, len)");
+				if ((x & 0xff) != (uint64_t)k) throw std::runtime_error(who + at + ": the low byte of x is " + std::to_string(x & 0xff) + ", not k");
+				if ((x >> 8) >> (2 * k)) throw std::runtime_error(who + at + ": the hash has 2k bits or more");
+				last = pos;
+			}
+		}
+		for (int g = 0; g < n_grp; ++g) {
+			std::vector<std::string> nm;
+			for (int64_t i = grp_off[g]; i < grp_off[g + 1]; ++i) nm.emplace_back(names[i]);
+			std::sort(nm.begin(), nm.end());
+			for (size_t i = 1; i < nm.size(); ++i) if (nm[i] == nm[i - 1]) throw std::runtime_error(who + "duplicate sequence name '" + nm[i] + "' inside a group (index.c:436 asserts uniqueness)");
+		}
+				mm_mapopt_t mo; mm_mapopt_init(&mo);
+		mo.flag = P.flag; mo.mid_occ = P.mid_occ; mo.mid_occ_frac = P.mid_occ_frac; mo.min_mid_occ = P.min_mid_occ; mo.max_mid_occ = P.max_mid_occ;
+		mo.max_max_occ = P.max_max_occ; mo.occ_dist = P.occ_dist; mo.q_occ_frac = P.q_occ_frac;
+		const std::string all_n((size_t)max_len + 1, 'N');
+		std::vector<const char*> seqs((size_t)n_seq, all_n.c_str());
+		std::unique_ptr<PgaIdx> ix(idx_build(w, k, n_seq, seqs.data(), lens, names, n_grp, grp_off, false));
+		ArenaScope arena_scope(ix->arena);
+		Minimizers &M = ix->M;
+		{
+			std::vector<u128> h((size_t)n_mz);
+			for (uint64_t j = 0; j < n_mz; ++j) h[j].x = mz_xy[2 * j], h[j].y = mz_xy[2 * j + 1];
+			if (n_mz) M.mz.upload(h, ix->st); else M.mz.alloc(1);
+			M.h_seq_off.assign(mz_off, mz_off + n_seq + 1);
+			M.seq_off.upload(M.h_seq_off, ix->st);
+			M.n = n_mz;
+			PGA_HIP(sync_stream(ix->st));
+		}
+		build_index_ex(ix->S, M, w, k, ix->I, ix->grp, ix->st);
+		ix->indexed = true;
+		const std::vector<int32_t> mo_grp = group_mid_occ(*ix, mo);
+		memcpy(mid_occ, mo_grp.data(), (size_t)n_grp * sizeof(int32_t));
+		ix->d_mid_occ.upload(mo_grp, ix->st);
+		if (own) { ix->d_own.upload(own, (size_t)n_seq, ix->st); PGA_HIP(sync_stream(ix->st)); }
+		SeedResult SR; SeedTap T; SR.tap = &T;
+		struct CountReplay { CountReplay() { front_routes_count_replay(true); } ~CountReplay() { front_routes_count_replay(false); } } count_replay;
+		seed_all(ix->S, M, ix->I, ix->grp, mo, ix->d_name_rank, ix->d_mid_occ, SR, ix->st, nullptr, own ? ix->d_own.p : nullptr, mode == 0);
+		PGA_HIP(sync_stream(ix->st));
+		// 0 dropped by the query filter, 1 seed used, 2 seed filtered; + 4: tandem
+		if (n_mz && T.keep.size() != n_mz) throw std::runtime_error(who + "seed_all left no filter verdicts");
+		uint64_t j = 0;
+		for (uint64_t i = 0; i < n_mz; ++i) {
+			if (!T.keep[i]) { state[i] = 0; continue; }
+			if (j >= T.sd_flag.size()) throw std::runtime_error(who + "seed_all left fewer seed flags than kept minimizers");
+			const uint8_t f = T.sd_flag[j++];
+			state[i] = (uint8_t)((f & 2 ? 2 : 1) | (f & 1 ? 4 : 0));
+		}
+		memcpy(rep_len, SR.h_rep_len.data(), (size_t)n_seq * sizeof(int32_t));
+		memcpy(anchor_off, SR.h_q_aoff.data(), ((size_t)n_seq + 1) * sizeof(uint64_t));
+		std::vector<uint64_t> flat((size_t)SR.n_a * 2);
+		if (SR.n_a) {
+			std::vector<u128> a = SR.a.download(ix->st);
+			for (size_t i = 0; i < (size_t)SR.n_a; ++i) flat[2 * i] = a[i].x, flat[2 * i + 1] = a[i].y;
+		}
+		*anchors_xy = dup_out(flat);
+		memset(q_tie, 0, (size_t)n_seq * sizeof(uint32_t));
+		if (mode == 1 && SR.n_a && SR.q_tie.p) { std::vector<uint32_t> t = SR.q_tie.download(ix->st); memcpy(q_tie, t.data(), (size_t)n_seq * sizeof(uint32_t)); }
+		return 0;
+	} catch (std::exception &e) { set_err(e.what()); return -1; }
+}
+static_assert(pga::FRONT_N_ROUTES == PGA_N_FRONT_ROUTES, "pga_stage_front_routes and the stages number the route counters alike");
+extern "C" void pga_stage_front_routes(int64_t out[PGA_N_FRONT_ROUTES]) { front_routes_take(out); }
 
 extern "C" int pga_stage_extd2(int32_t n_jobs, const uint8_t *const *q, const int32_t *qlen, const uint8_t *const *t, const int32_t *tlen,
                                int a, int b, int sc_ambi, int gapo, int gape, int gapo2, int gape2, const int32_t *w, const int32_t *zdrop, const int32_t *end_bonus, const int32_t *flag,

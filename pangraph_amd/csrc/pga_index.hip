@@ -12,8 +12,14 @@
 #include "pga_pipeline.h"
 #include "pga_maxocc_hist.h"
 #include <rocprim/rocprim.hpp>
+#include <atomic>
 
 namespace pga {
+
+// Route counters of the stage tap pga_stage_front_routes (tests): which branch of the sketch, the index build, mid_occ and the anchor sort answered.
+static std::atomic<int64_t> g_front_routes[FRONT_N_ROUTES];
+void front_route_add(int which, int64_t n) { g_front_routes[which].fetch_add(n, std::memory_order_relaxed); }
+void front_routes_take(int64_t out[FRONT_N_ROUTES]) { for (int i = 0; i < FRONT_N_ROUTES; ++i) out[i] = g_front_routes[i].exchange(0); }
 
 __global__ void k_split(const u128 *__restrict__ mz, uint64_t n, uint64_t *__restrict__ kx, uint64_t *__restrict__ vy)
 {
@@ -155,6 +161,7 @@ void build_index_ex(const SeqSet &S, const Minimizers &M, int w, int k, Index &I
 			I.key_grp.alloc(n_keys);
 			hipLaunchKernelGGL(k_groups_ck, dim3(nb), dim3(256), 0, st, ck2.p, hash_bits, flag.p, gid.p, orig2.p, vy.p, n, I.key.p, I.occ_off.p, I.key_grp.p, grp_of_mz.p, I.occ.p);
 			PGA_HIP(hipGetLastError());
+			front_route_add(FR_IDX_ONE_SORT);
 			return;                                                              // (no wait: the scratch of this scope goes back to the call's arena, reused in stream order)
 		}
 	}
@@ -165,7 +172,11 @@ void build_index_ex(const SeqSet &S, const Minimizers &M, int w, int k, Index &I
 	{
 		size_t tmp_bytes = 0;
 		// x = hash << 8 | span with a 2k-bit hash and span == k for every minimizer (sketch.c:136 without HPC): only bits [8, 8+2k) vary
-		const int lo_bit = 8, hi_bit = std::min(64, 8 + 2 * k);
+		// With k = 28 the range would be [8, 64): rocprim's merge-sort route (1 024 < n <= its merge_sort_limit) builds the mask of a partial range
+		// [b, e) from T(1) << e, which is undefined at e = 64 and comes out as a mask of the low byte alone -- the blocks of 1 024 were sorted, then
+		// merged as if all keys were equal, and a hash's copies from different blocks ended up in different lists (tests/test_gpu_seed.py, the
+		// 300 groups at k = 28).  The whole word is sorted then: the low byte is the same in every key.
+		const int hi_bit = std::min(64, 8 + 2 * k), lo_bit = hi_bit == 64 ? 0 : 8;
 		PGA_HIP(rocprim::radix_sort_pairs(nullptr, tmp_bytes, kx.p, kx2.p, orig.p, orig2.p, n, lo_bit, hi_bit, st));
 		DBuf<uint8_t> tmp(tmp_bytes ? tmp_bytes : 1);
 		PGA_HIP(rocprim::radix_sort_pairs(tmp.p, tmp_bytes, kx.p, kx2.p, orig.p, orig2.p, n, lo_bit, hi_bit, st));
@@ -206,6 +217,7 @@ void build_index_ex(const SeqSet &S, const Minimizers &M, int w, int k, Index &I
 	PGA_HIP(hipMemcpyAsync(I.occ_off.p + n_keys, &n32, 4, hipMemcpyHostToDevice, st));
 	PGA_HIP(hipGetLastError());
 	PGA_HIP(sync_stream(st));
+	front_route_add(FR_IDX_TWO_SORTS);
 }
 
 // comp = group << cbits | occurrence count: a count never exceeds the number of indexed minimizers, so cbits = bit length of n_occ holds it
@@ -250,8 +262,9 @@ std::vector<int32_t> index_cal_max_occ(const SeqSet &S, const Index &I, float f,
 		std::vector<int32_t> sel = d_sel.download(st);
 		bool resolved = true;
 		for (int32_t v : sel) if (v < 0) { resolved = false; break; }
-		if (resolved) return sel;
+		if (resolved) { front_route_add(FR_MO_HIST); return sel; }
 	}
+	front_route_add(FR_MO_SORT);
 	DBuf<uint64_t> comp(n), comp2(n);
 	int cbits = 1; while (cbits < 32 && (I.n_occ >> cbits) != 0) ++cbits;        // counts are <= n_occ < 2^32
 	int gbits = 0; while (gbits < 32 && (1LL << gbits) < S.n_grp) ++gbits;       // groups are < n_grp

@@ -35,7 +35,19 @@ struct SeedResult {
 	bool exact = true;                          // false: tied queries are still in stable order
 	DBuf<uint64_t> raw_x, raw_y, srt_x, srt_y;
 	DBuf<uint32_t> dupc, q_tie;
+	struct SeedTap *tap = nullptr;              // tests only (pga_stage_seed); a batch passes none and nothing changes for it
 };
+// What the minimizer-level tap asks of seed_all besides the anchors: the query filter's verdict per minimizer and the flags of every seed.
+struct SeedTap {
+	std::vector<uint32_t> keep;      // per minimizer: 1 = left by the query-side filter (k_mz_keep)
+	std::vector<uint8_t> sd_flag;    // per kept minimizer, in order: bit 0 tandem, bit 1 filtered (k_seed_make, k_seed_select)
+};
+// route counters of the stages in front of chaining (pga_stage_front_routes), in this order.  Host-side atomics next to the launches they count: process-wide, and
+// neither a launch nor a copy is added for them.  FR_REPLAY_Q needs the replay's flags on the host, so it is counted only while front_routes_count_replay(true) holds (the tap).
+enum { FR_SK_TILES8_19 = 0, FR_SK_TILES8_10, FR_SK_TILES, FR_SK_SERIAL, FR_SK_RETRY, FR_IDX_ONE_SORT, FR_IDX_TWO_SORTS, FR_MO_HIST, FR_MO_SORT, FR_REPLAY_Q, FRONT_N_ROUTES };
+void front_route_add(int which, int64_t n = 1);
+void front_routes_take(int64_t out[FRONT_N_ROUTES]);   // the counters since the last call, zeroed
+void front_routes_count_replay(bool on);               // of the calling thread
 
 void build_index_ex(const SeqSet &S, const Minimizers &M, int w, int k, Index &I, DBuf<uint32_t> &grp_of_mz, hipStream_t st);
 void seed_all(const SeqSet &S, const Minimizers &M, const Index &I, const DBuf<uint32_t> &grp_of_mz, const mm_mapopt_t &opt,

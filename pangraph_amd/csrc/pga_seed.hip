@@ -343,6 +343,7 @@ void seed_all(const SeqSet &S, const Minimizers &M, const Index &I, const DBuf<u
 	} else {
 		PGA_HIP(hipMemcpyAsync(seq_off2.p, M.seq_off.p, ((size_t)n_seq + 1) * 8, hipMemcpyDeviceToDevice, st));
 	}
+	if (O.tap) O.tap->keep = keep.download(st);
 	if (n_kept == 0) { O.a.alloc(1); return; }
 
 	// 2. seeds, selection, rep_len
@@ -372,6 +373,7 @@ void seed_all(const SeqSet &S, const Minimizers &M, const Index &I, const DBuf<u
 	uint64_t n_ub = 0;
 	PGA_HIP(hipMemcpyAsync(&n_ub, ub_off.p + n_kept, 8, hipMemcpyDeviceToHost, st));
 	PGA_HIP(sync_stream(st));
+	if (O.tap) O.tap->sd_flag = sd_flag.download(st);
 	DBuf<u128> ub(n_ub ? n_ub : 1);
 	hipLaunchKernelGGL(k_anchors, dim3(nbk), dim3(256), 0, st, M.mz.p, kept_p, n_kept, sd_n.p, sd_occ.p, sd_qpos.p, sd_flag.p, I.occ.p, C,
 	                   (int32_t)I.k, cnt.p, ub_off.p, ub.p);
@@ -454,11 +456,15 @@ __global__ void k_need_tied(const uint32_t *__restrict__ q_tie, const uint32_t *
 	if (q < n_seq) out[q] = q_tie[q] && (!need || need[q]) ? 1u : 0u;
 }
 
+static thread_local bool t_count_replay = false;
+void front_routes_count_replay(bool on) { t_count_replay = on; }
+
 void seed_exact_order(SeedResult &O, const uint32_t *d_need, int n_seq, hipStream_t st, Timers *tm)
 {
 	if (O.n_a == 0 || !O.q_tie.p || !O.raw_x.p) return;
 	DBuf<uint32_t> fl((size_t)n_seq);
 	hipLaunchKernelGGL(k_need_tied, dim3((unsigned)((n_seq + 255) / 256)), dim3(256), 0, st, O.q_tie.p, d_need, n_seq, fl.p);
+	if (t_count_replay) { int64_t c = 0; for (uint32_t v : fl.download(st)) c += v != 0; front_route_add(FR_REPLAY_Q, c); }   // (the tap only: a batch never copies the flags)
 	// queries whose anchors hold equal keys restart from the raw order and go through the replay of radix_sort_128x (pga_sort_replay.hip); the stable
 	// sort doubles as its hint: buckets without equal keys are copied from it instead of being walked
 	hipLaunchKernelGGL(k_copy_tied, dim3((unsigned)n_seq, 64), dim3(256), 0, st, n_seq, fl.p, O.q_aoff.p, O.raw_x.p, O.raw_y.p, O.a.p);

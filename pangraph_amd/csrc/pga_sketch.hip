@@ -21,6 +21,7 @@
 #include <chrono>
 #include "pga_common.h"
 #include "pga_wave.h"
+#include "pga_pipeline.h"
 #include <sched.h>
 #include <unistd.h>
 #include <atomic>
@@ -103,16 +104,16 @@ static inline uint8_t nt4_host(uint8_t r)
 {
 	uint8_t c = r & 0xdf;
 	uint8_t code = c == 'A' ? 0 : c == 'C' ? 1 : c == 'G' ? 2 : (c == 'T' || c == 'U') ? 3 : 4;
-	if (r < 0x40) code = 4;
+	if (r < 0x40) code = r < 4 ? r : 4;       // (the table's first four entries are 0 1 2 3: bytes 0..3 are bases too)
 	return code;
 }
 
-// ASCII -> bases (sketch.c:9-26 table: A/a 0, C/c 1, G/g 2, T/t/U/u 3, everything else 4), sixteen bases per thread
+// bytes -> bases (sketch.c:9-26 table: A/a 0, C/c 1, G/g 2, T/t/U/u 3, the bytes 0..3 themselves, everything else 4), sixteen bases per thread
 __device__ __forceinline__ uint32_t nt4_of(uint32_t r)
 {
 	const uint32_t c = r & 0xdf;
 	uint32_t code = c == 'A' ? 0u : c == 'C' ? 1u : c == 'G' ? 2u : (c == 'T' || c == 'U') ? 3u : 4u;
-	if (r < 0x40) code = 4u;
+	if (r < 0x40) code = r < 4u ? r : 4u;     // (the table's first four entries are 0 1 2 3: bytes 0..3 are bases too)
 	return code;
 }
 // The resident store: 2 bits per base, sixteen bases per 32-bit word, plus one "not ACGT" bit per base (the reference packs its index
@@ -735,6 +736,7 @@ void sketch_all(const SeqSet &S, int w, int k, Minimizers &M, hipStream_t st, Ti
 			// eight consecutive positions per thread where w is one of the presets' (asm5/asm10: 19, asm20: 10) and a key fits 64 bits
 			static const bool no8 = getenv("PGA_SKETCH_STRIDED") != nullptr;
 			const bool fit8 = !no8 && 2 * k + 13 <= 64 && 8 * ((w + 7) / 8) + w + k <= SK8_HALO;
+			front_route_add(fit8 && w == 19 ? FR_SK_TILES8_19 : fit8 && w == 10 ? FR_SK_TILES8_10 : FR_SK_TILES);
 			if (fit8 && w == 19) hipLaunchKernelGGL((k_sketch_tiles8<19>), dim3((unsigned)nt), dim3(SK_THREADS), 0, st, S.d_pk2.p, S.d_nmask.p, S.d_off.p, S.d_len.p, d_tiles.p, k, stage.p, cap, d_cnt.p, d_ovf.p);
 			else if (fit8 && w == 10) hipLaunchKernelGGL((k_sketch_tiles8<10>), dim3((unsigned)nt), dim3(SK_THREADS), 0, st, S.d_pk2.p, S.d_nmask.p, S.d_off.p, S.d_len.p, d_tiles.p, k, stage.p, cap, d_cnt.p, d_ovf.p);
 			else hipLaunchKernelGGL((k_sketch_tiles<63>), dim3((unsigned)nt), dim3(SK_THREADS), 0, st,
@@ -746,7 +748,7 @@ void sketch_all(const SeqSet &S, int w, int k, Minimizers &M, hipStream_t st, Ti
 			std::vector<int> h_ovf; std::vector<uint64_t> h_tot;
 			{ Downloads dl(st); dl.add(h_ovf, d_ovf.p, 1); dl.add(h_tot, d_toff.p + nt, 1); dl.wait(); }
 			const double k_ms = et.finish(K_SKETCH);
-			if (h_ovf[0]) { cap *= 4; d_ovf.zero(st); d_cnt.zero(st); continue; }  // retry with bigger slabs
+			if (h_ovf[0]) { front_route_add(FR_SK_RETRY); cap *= 4; d_ovf.zero(st); d_cnt.zero(st); continue; }  // retry with bigger slabs
 			const uint64_t total = h_tot[0];
 			M.n = total;
 			if (tm) { tm->kern[K_SKETCH].ms += k_ms; tm->kern[K_SKETCH].launches += 1; tm->kern[K_SKETCH].alg_bytes += 0.375 * (double)S.total + 16.0 * (double)total; }   // packed bases in (2 bits + the N bit), minimizers out
@@ -765,6 +767,7 @@ void sketch_all(const SeqSet &S, int w, int k, Minimizers &M, hipStream_t st, Ti
 	} else {
 		DBuf<uint64_t> d_cnt((size_t)n + 1); d_cnt.zero(st);
 		DBuf<u128> ring((size_t)n * 256);
+		front_route_add(FR_SK_SERIAL, 2);          // (a counting launch and a writing one)
 		hipLaunchKernelGGL(k_sketch_serial, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, st, S.bases(), S.d_off.p, S.d_len.p, n, w, k,
 		                   (u128*)nullptr, (const uint64_t*)nullptr, d_cnt.p, ring.p);
 		exclusive_scan_u64(d_cnt.p, M.seq_off.p, (size_t)n + 1, st);
