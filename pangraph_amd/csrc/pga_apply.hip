@@ -14,37 +14,14 @@
 // The kernels and the host tables are pga_apply_idx.h (no wave intrinsic: tests/emu/apply_emu.cpp runs them on the host).
 // All arithmetic is integer; atomics feed only counts and minima, so the result does not depend on the launch geometry.
 #include "pga_common.h"
+#include "pga_graph_host.h"
 #include "../../include/pga_align.h"
 #include "pga_apply_idx.h"
-#include <rocprim/rocprim.hpp>
 #include <numeric>
 
 namespace pga {
 
-static void ap_excl_scan(const uint32_t *in, uint32_t *out, size_t n, hipStream_t st)
-{
-	size_t tb = 0;
-	PGA_HIP(rocprim::exclusive_scan(nullptr, tb, in, out, 0u, n, rocprim::plus<uint32_t>(), st));
-	DBuf<uint8_t> tmp(tb + 16);
-	PGA_HIP(rocprim::exclusive_scan(tmp.p, tb, in, out, 0u, n, rocprim::plus<uint32_t>(), st));
-}
-template <class K> static void ap_sort_pairs(const K *kin, K *kout, const uint32_t *vin, uint32_t *vout, size_t n, unsigned bits, hipStream_t st)
-{
-	if (!n) return;
-	size_t tb = 0;
-	PGA_HIP(rocprim::radix_sort_pairs(nullptr, tb, kin, kout, vin, vout, n, 0, bits, st));
-	DBuf<uint8_t> tmp(tb + 16);
-	PGA_HIP(rocprim::radix_sort_pairs(tmp.p, tb, kin, kout, vin, vout, n, 0, bits, st));
-}
-template <class T> static T *ap_host_array(uint64_t n)
-{
-	T *p = (T*)calloc((size_t)(n ? n : 1), sizeof(T));
-	if (!p) throw std::runtime_error("pga_apply_merge: out of host memory");
-	return p;
-}
-static unsigned ap_grid(uint64_t items) { return (unsigned)std::min<uint64_t>(std::max<uint64_t>((items + TP_THREADS - 1) / TP_THREADS, 1), 2048); }
-template <class T> static void ap_up(DBuf<T> &d, const T *h, uint64_t n, hipStream_t st) { if (n) PGA_HIP(hipMemcpyAsync(d.p, h, n * sizeof(T), hipMemcpyHostToDevice, st)); }
-template <class T> static void ap_fetch(T *dst, const T *src, uint64_t n, hipStream_t st) { if (n) PGA_HIP(hipMemcpyAsync(dst, src, n * sizeof(T), hipMemcpyDeviceToHost, st)); }
+static unsigned ap_grid(uint64_t items) { return grid_for(items, TP_THREADS, 2048); }
 
 void apply_merge_host(int64_t n_blocks, const pga_topo_block_t *blocks, int64_t n_paths, const pga_topo_path_t *paths, int64_t n_nodes, const pga_topo_node_t *nodes,
                       int64_t n_cut, const pga_apply_cut_t *cut, const pga_plan_interval_t *intervals, const pga_slice_res_t *slices, const pga_slice_member_t *members,
@@ -62,15 +39,15 @@ void apply_merge_host(int64_t n_blocks, const pga_topo_block_t *blocks, int64_t 
 	DBuf<uint32_t> d_depth(nb + 1), d_first(nb + 1), d_cutof(nb + 1), d_matoff(nc + 1), d_ivcut(ni + 1), d_iventry(ni + 1), d_survrank(nb + 1), d_iota(std::max(nm, ne) + 1);
 	DBuf<pga_apply_cut_t> d_cut(nc + 1); DBuf<pga_plan_interval_t> d_iv(ni + 1); DBuf<pga_slice_res_t> d_slices(ni + 1); DBuf<pga_slice_member_t> d_members(nm + 1);
 	DBuf<ApEntry> d_entries(ne + 1); DBuf<tp_u64> d_eids(ne + 1), d_seids(ne + 1), d_survids(ns + 1);
-	ap_up(d_nodes, nodes, nn, st); ap_up(d_paths, paths, np, st); ap_up(d_blocks, blocks, nb, st);
-	ap_up(d_depth, A.T.depth.data(), nb, st); ap_up(d_first, A.T.slot_first.data(), nb + 1, st); ap_up(d_cutof, A.cut_of.data(), nb, st);
-	ap_up(d_matoff, A.mat_off.data(), nc + 1, st); ap_up(d_ivcut, A.iv_cut.data(), ni, st); ap_up(d_iventry, A.iv_entry.data(), ni, st);
-	ap_up(d_survrank, A.surv_rank.data(), nb, st); ap_up(d_cut, cut, nc, st); ap_up(d_iv, intervals, ni, st); ap_up(d_slices, slices, ni, st);
-	ap_up(d_members, members, nm, st); ap_up(d_entries, A.entries.data(), ne, st); ap_up(d_eids, (const tp_u64*)A.entry_ids.data(), ne, st);
-	ap_up(d_survids, (const tp_u64*)A.surv_ids.data(), ns, st);
+	upload(d_nodes, nodes, nn, st); upload(d_paths, paths, np, st); upload(d_blocks, blocks, nb, st);
+	upload(d_depth, A.T.depth.data(), nb, st); upload(d_first, A.T.slot_first.data(), nb + 1, st); upload(d_cutof, A.cut_of.data(), nb, st);
+	upload(d_matoff, A.mat_off.data(), nc + 1, st); upload(d_ivcut, A.iv_cut.data(), ni, st); upload(d_iventry, A.iv_entry.data(), ni, st);
+	upload(d_survrank, A.surv_rank.data(), nb, st); upload(d_cut, cut, nc, st); upload(d_iv, intervals, ni, st); upload(d_slices, slices, ni, st);
+	upload(d_members, members, nm, st); upload(d_entries, A.entries.data(), ne, st); upload(d_eids, (const tp_u64*)A.entry_ids.data(), ne, st);
+	upload(d_survids, (const tp_u64*)A.surv_ids.data(), ns, st);
 	std::vector<uint32_t> iota(std::max(nm, ne) + 1);
 	std::iota(iota.begin(), iota.end(), 0u);
-	ap_up(d_iota, iota.data(), iota.size(), st);
+	upload(d_iota, iota.data(), iota.size(), st);
 	// ---- the checks of the graph, as pga_plan_simplify makes them ----
 	DBuf<uint32_t> d_pathof(nn + 1), d_cnts(A.T.n_slots + nb + 1), d_terr(TP_ERRS), d_err(AP_ERRS);
 	DBuf<tp_u64> d_key(nn + 1);
@@ -106,19 +83,19 @@ void apply_merge_host(int64_t n_blocks, const pga_topo_block_t *blocks, int64_t 
 	const unsigned g_mem = ap_grid(nm), g_pos = ap_grid(nn), g_ent = ap_grid(ne + 1);
 	hipLaunchKernelGGL(k_apply_slot_pos, dim3(g_pos), dim3(TP_THREADS), 0, st, V);
 	hipLaunchKernelGGL(k_apply_members, dim3(g_mem), dim3(TP_THREADS), 0, st, V);
-	ap_sort_pairs(d_eids.p, d_seids.p, d_iota.p, d_sentry.p, ne, 64, st);
+	radix_sort_pairs(d_eids.p, d_seids.p, d_iota.p, d_sentry.p, ne, 64, st);
 	hipLaunchKernelGGL(k_apply_entries, dim3(g_ent), dim3(TP_THREADS), 0, st, V);
 	hipLaunchKernelGGL(k_apply_survivors, dim3(ap_grid(nb)), dim3(TP_THREADS), 0, st, V);
-	ap_excl_scan(d_rdepth.p, d_rmoff.p, ne + 1, st);
+	excl_scan(d_rdepth.p, d_rmoff.p, ne + 1, st);
 	hipLaunchKernelGGL(k_apply_new_blocks, dim3(g_ent), dim3(TP_THREADS), 0, st, V);
-	ap_sort_pairs(d_nkey.p, d_nkey_s.p, d_iota.p, d_byid.p, nm, 64, st);
+	radix_sort_pairs(d_nkey.p, d_nkey_s.p, d_iota.p, d_byid.p, nm, 64, st);
 	hipLaunchKernelGGL(k_apply_key2, dim3(g_mem), dim3(TP_THREADS), 0, st, V);
-	ap_sort_pairs(d_key2.p, d_key2s.p, d_byid.p, d_byslot.p, nm, 32, st);
+	radix_sort_pairs(d_key2.p, d_key2s.p, d_byid.p, d_byslot.p, nm, 32, st);
 	hipLaunchKernelGGL(k_apply_slots, dim3(g_mem), dim3(TP_THREADS), 0, st, V);
 	PGA_HIP(hipGetLastError());
 	// ---- the first wait: nothing behind it runs on input that was not checked ----
 	uint32_t terr[TP_ERRS], err[AP_ERRS];
-	ap_fetch(terr, (const uint32_t*)d_terr.p, TP_ERRS, st); ap_fetch(err, (const uint32_t*)d_err.p, AP_ERRS, st);
+	fetch(terr, (const uint32_t*)d_terr.p, TP_ERRS, st); fetch(err, (const uint32_t*)d_err.p, AP_ERRS, st);
 	PGA_HIP(sync_stream(st));
 	ap_report(terr, err);
 	// ---- the new nodes in path order, cnt[] / repl[], the tile sums ----
@@ -126,7 +103,7 @@ void apply_merge_host(int64_t n_blocks, const pga_topo_block_t *blocks, int64_t 
 	DBuf<pga_topo_node_t> d_ordered(nm + 1), d_nodes2(nn + 1), d_onodes(n_out + 1); DBuf<pga_topo_path_t> d_opaths(np + 1);
 	DBuf<uint32_t> d_cnt(nn + 1), d_repl(nn + 1), d_tsum(n_tiles + 1), d_toff(n_tiles + 1), d_poff(nn + 1);
 	V.ordered = d_ordered.p; V.nodes2 = d_nodes2.p; V.cnt = d_cnt.p; V.repl = d_repl.p;
-	ap_excl_scan(d_mat.p, d_matscan.p, A.n_mat + 1, st);
+	excl_scan(d_mat.p, d_matscan.p, A.n_mat + 1, st);
 	hipLaunchKernelGGL(k_apply_order, dim3(g_mem), dim3(TP_THREADS), 0, st, V);
 	hipLaunchKernelGGL(k_apply_positions, dim3(g_pos), dim3(TP_THREADS), 0, st, V);
 	d_poff.zero(st); d_toff.zero(st);
@@ -138,20 +115,20 @@ void apply_merge_host(int64_t n_blocks, const pga_topo_block_t *blocks, int64_t 
 		hipLaunchKernelGGL(k_topo_tile_scan, dim3(1), dim3(TP_THREADS), 0, st, T);
 	}
 	PGA_HIP(hipGetLastError());
-	ap_fetch(&total, (const uint32_t*)d_toff.p + n_tiles, 1, st);
+	fetch(&total, (const uint32_t*)d_toff.p + n_tiles, 1, st);
 	PGA_HIP(sync_stream(st));
 	if (total != n_out) ap_fail("internal: the splice counts " + std::to_string(total) + " nodes, " + std::to_string(n_out) + " expected");   // (before it writes one)
 	if (n_tiles) hipLaunchKernelGGL(k_topo_splice, dim3(std::min<uint32_t>(n_tiles, 2048u)), dim3(TP_THREADS), 0, st, T);
 	hipLaunchKernelGGL(k_topo_paths, dim3(ap_grid(np)), dim3(TP_THREADS), 0, st, T);
 	PGA_HIP(hipGetLastError());
 	// ---- the output ----
-	out->new_nodes = ap_host_array<pga_topo_node_t>(nm); out->old_node = ap_host_array<uint64_t>(nm); out->member_src = ap_host_array<uint64_t>(nm);
-	out->new_blocks = ap_host_array<pga_apply_block_t>(ne); out->block_map = ap_host_array<uint32_t>(nb);
-	out->paths = ap_host_array<pga_topo_path_t>(np); out->nodes = ap_host_array<pga_topo_node_t>(n_out); out->blocks = ap_host_array<pga_topo_block_t>(nb_out);
-	ap_fetch(out->new_nodes, (const pga_topo_node_t*)d_new.p, nm, st); ap_fetch(out->old_node, (const uint64_t*)d_old.p, nm, st);
-	ap_fetch(out->member_src, (const uint64_t*)d_msrc.p, nm, st); ap_fetch(out->new_blocks, (const pga_apply_block_t*)d_onew.p, ne, st);
-	ap_fetch(out->block_map, (const uint32_t*)d_bmap.p, nb, st); ap_fetch(out->paths, (const pga_topo_path_t*)d_opaths.p, np, st);
-	ap_fetch(out->nodes, (const pga_topo_node_t*)d_onodes.p, n_out, st); ap_fetch(out->blocks, (const pga_topo_block_t*)d_oblocks.p, nb_out, st);
+	out->new_nodes = host_array<pga_topo_node_t>(nm, "pga_apply_merge"); out->old_node = host_array<uint64_t>(nm, "pga_apply_merge"); out->member_src = host_array<uint64_t>(nm, "pga_apply_merge");
+	out->new_blocks = host_array<pga_apply_block_t>(ne, "pga_apply_merge"); out->block_map = host_array<uint32_t>(nb, "pga_apply_merge");
+	out->paths = host_array<pga_topo_path_t>(np, "pga_apply_merge"); out->nodes = host_array<pga_topo_node_t>(n_out, "pga_apply_merge"); out->blocks = host_array<pga_topo_block_t>(nb_out, "pga_apply_merge");
+	fetch(out->new_nodes, (const pga_topo_node_t*)d_new.p, nm, st); fetch(out->old_node, (const uint64_t*)d_old.p, nm, st);
+	fetch(out->member_src, (const uint64_t*)d_msrc.p, nm, st); fetch(out->new_blocks, (const pga_apply_block_t*)d_onew.p, ne, st);
+	fetch(out->block_map, (const uint32_t*)d_bmap.p, nb, st); fetch(out->paths, (const pga_topo_path_t*)d_opaths.p, np, st);
+	fetch(out->nodes, (const pga_topo_node_t*)d_onodes.p, n_out, st); fetch(out->blocks, (const pga_topo_block_t*)d_oblocks.p, nb_out, st);
 	PGA_HIP(sync_stream(st));
 	out->n_new_nodes = (int64_t)nm; out->n_new_blocks = (int64_t)ne; out->n_blocks = (int64_t)nb_out; out->n_paths = n_paths; out->n_nodes = (int64_t)n_out;
 }

@@ -2,7 +2,8 @@
 // Pangraph::update, pangraph.rs:68-107, applied block after block, reweave.rs:445-450, and the insertion of the merged blocks,
 // graph_merging.rs:156-165).  No wave intrinsic, atomicAdd / atomicMin only: all of this compiles under hipcc and, with dev/emu/hip_emu.h
 // included first, under g++ -std=c++17 -DPGA_EMU (tests/emu/apply_emu.cpp runs it against a direct scalar construction).
-// The path lookup, the node hash and the tiled splice are pga_topo_idx.h's; the sorts and scans are rocPRIM's (pga_apply.hip).
+// The path lookup, the node hash and the tiled splice (its workgroup scan: pga_tile_scan.h) are pga_topo_idx.h's; the sorts and scans are
+// rocPRIM's (pga_apply.hip).
 //
 // A MEMBER here is a kept slice member, index k into slice.members[]; its SLOT is (cut block, member) of the graph, named by one position.
 // The MATRIX has one word per (cut block, member, interval of that block), rows of n_intervals words, cut after cut: a kept member counts

@@ -3,14 +3,14 @@
 // the merged blocks (graph_merging.rs:156-165) and the blocks split_block leaves (reweave.rs:359-401), for the whole graph after in one call.
 // The reference inserts member after member into a BTreeMap per block; here an output MEMBER, a LIST ELEMENT and a LETTER are the units of work.
 //   host               validation (all of it before anything is launched), one record per output block, the consensus pointers; one upload
-//   k_assemble_tile_sums / _tile_scan / _offsets <before>   three exclusive sums over the members before: where a survivor's lists start
+//   k_ts_sums / _scan / _offsets (pga_tile_scan.h), before   three exclusive sums over the members before: where a survivor's lists start
 //   k_assemble_desc    one thread per output member: its source, its counts, its first elements there; member_src, res[].status and the
 //                      offsets of the records are checked here
 //   k_assemble_who / _who_check   one thread per node after, one per slot: who[], every slot named exactly once
-//   k_assemble_tile_sums / _tile_scan / _offsets <out>      three exclusive sums over the descriptors: where the lists start in the output
+//   k_ts_sums / _scan / _offsets, out      three exclusive sums over the descriptors: where the lists start in the output
 //   host               the first wait: the checks, the three list totals
 //   k_assemble_copy<list>   one thread per element of an output list (never one thread per member: a member has no edit or 10^4)
-//   k_assemble_tile_sums / _tile_scan / _offsets <letters>  the lengths of the output insertions
+//   k_ts_sums / _scan / _offsets, letters  the lengths of the output insertions
 //   host               the second wait: the bounds of every insertion (checked by the copy), the letter total
 //   k_assemble_letters one thread per letter; k_assemble_seq_off
 //   host               the third wait: the output
@@ -18,50 +18,18 @@
 // The kernels and the host tables are pga_assemble_idx.h (no wave intrinsic: tests/emu/assemble_emu.cpp runs them on the host).
 // All arithmetic is integer; atomics feed only marks and minima, so the result does not depend on the launch geometry.
 #include "pga_common.h"
+#include "pga_graph_host.h"
 #include "../../include/pga_align.h"
 #include "pga_assemble_idx.h"
 
 namespace pga {
 
-template <class T> static T *as_host_array(uint64_t n)
-{
-	T *p = (T*)calloc((size_t)(n ? n : 1), sizeof(T));
-	if (!p) throw std::runtime_error("pga_assemble_blocks: out of host memory");
-	return p;
-}
-static unsigned as_grid(uint64_t items) { return (unsigned)std::min<uint64_t>(std::max<uint64_t>((items + AS_THREADS - 1) / AS_THREADS, 1), 2048); }
-static unsigned as_tile_grid(uint64_t items) { return (unsigned)std::min<uint64_t>(std::max<uint64_t>((items + AS_TILE - 1) / AS_TILE, 1), 1u << 16); }
-template <class T> static void as_up(DBuf<T> &d, const T *h, uint64_t n, hipStream_t st) { if (n) PGA_HIP(hipMemcpyAsync(d.p, h, n * sizeof(T), hipMemcpyHostToDevice, st)); }
-template <class T> static void as_fetch(T *dst, const T *src, uint64_t n, hipStream_t st) { if (n) PGA_HIP(hipMemcpyAsync(dst, src, n * sizeof(T), hipMemcpyDeviceToHost, st)); }
-
-// the scan's buffers: every one an entry longer than its count, none is empty
-struct AsScanBufs {
-	DBuf<as_u64> tile_sum, tile_off, off;
-	RmScan make(uint64_t n, uint32_t n_q)
-	{
-		const uint32_t n_tiles = (uint32_t)((n + AS_TILE - 1) / AS_TILE);
-		tile_sum.alloc((uint64_t)n_q * n_tiles + 1); tile_off.alloc((uint64_t)n_q * (n_tiles + 1)); off.alloc((uint64_t)n_q * (n + 1));
-		return RmScan{n, n_tiles, n_q, tile_sum.p, tile_off.p, off.p};
-	}
-};
-template <int K> static void as_scan(const AsDev &V, hipStream_t st)
-{
-	const uint32_t n_tiles = V.scan[K].n_tiles;
-	if (n_tiles) hipLaunchKernelGGL(k_assemble_tile_sums<K>, dim3(std::min<uint32_t>(n_tiles, 2048u)), dim3(AS_THREADS), 0, st, V);
-	hipLaunchKernelGGL(k_assemble_tile_scan<K>, dim3(1), dim3(AS_THREADS), 0, st, V);
-	if (n_tiles) hipLaunchKernelGGL(k_assemble_offsets<K>, dim3(std::min<uint32_t>(n_tiles, 2048u)), dim3(AS_THREADS), 0, st, V);
-}
+static unsigned as_grid(uint64_t items) { return grid_for(items, AS_THREADS, 2048); }
+static unsigned as_tile_grid(uint64_t items) { return grid_for(items, AS_TILE, 1u << 16); }
 
 // the stream's clock at four places of the last call of this thread: upload, kernels (their waits included), download, in ms
 static thread_local double g_as_ms[3] = {0, 0, 0};
 void assemble_last_ms(double *ms) { for (int i = 0; i < 3; ++i) ms[i] = g_as_ms[i]; }
-struct AsClock {
-	hipEvent_t e[4]; hipStream_t st;
-	explicit AsClock(hipStream_t s) : st(s) { for (hipEvent_t &x : e) PGA_HIP(hipEventCreate(&x)); }
-	void at(int i) { PGA_HIP(hipEventRecord(e[i], st)); }
-	void read() { for (int i = 0; i < 3; ++i) { float ms = 0; PGA_HIP(hipEventElapsedTime(&ms, e[i], e[i + 1])); g_as_ms[i] = ms; } }
-	~AsClock() { for (hipEvent_t &x : e) (void)hipEventDestroy(x); }
-};
 
 void assemble_blocks_host(int64_t n_blocks, const pga_rc_block_t *rc_blocks, const pga_rc_member_t *members, const pga_sub_t *subs, const pga_del_t *dels,
                           const pga_ins_t *inss, const char *ins_seq, uint64_t ins_seq_len, int64_t n_cut, const pga_apply_cut_t *cut, const pga_plan_interval_t *intervals,
@@ -79,17 +47,17 @@ void assemble_blocks_host(int64_t n_blocks, const pga_rc_block_t *rc_blocks, con
 	const uint64_t nn = A.identity ? 0 : (uint64_t)applied->n_nodes;
 	const bool who = !A.identity;
 	out->n_blocks = (int64_t)nbo; out->n_members = (int64_t)nmo;
-	out->blocks = as_host_array<pga_rc_block_t>(nbo);
+	out->blocks = host_array<pga_rc_block_t>(nbo, "pga_assemble_blocks");
 	std::copy(A.o_blocks.begin(), A.o_blocks.end(), out->blocks);
-	out->members = as_host_array<pga_rc_member_t>(nmo); out->origin = as_host_array<int64_t>(nmo);
-	if (who) out->who = as_host_array<pga_detach_member_t>(nmo);
+	out->members = host_array<pga_rc_member_t>(nmo, "pga_assemble_blocks"); out->origin = host_array<int64_t>(nmo, "pga_assemble_blocks");
+	if (who) out->who = host_array<pga_detach_member_t>(nmo, "pga_assemble_blocks");
 	if (nmo == 0) {                                                           // no member after: nothing to gather, no slot to hold a node against, no device call
-		out->subs = as_host_array<pga_sub_t>(0); out->dels = as_host_array<pga_del_t>(0); out->inss = as_host_array<pga_ins_t>(0); out->ins_seq = as_host_array<char>(0);
+		out->subs = host_array<pga_sub_t>(0, "pga_assemble_blocks"); out->dels = host_array<pga_del_t>(0, "pga_assemble_blocks"); out->inss = host_array<pga_ins_t>(0, "pga_assemble_blocks"); out->ins_seq = host_array<char>(0, "pga_assemble_blocks");
 		return;
 	}
 	StreamLease stream;
 	hipStream_t st = stream.s;
-	AsClock clock(st);
+	StageClock clock(st);
 	clock.at(0);
 	// ---- the uploads (every buffer one entry longer than its count: none is empty) ----
 	DBuf<AsBlock> d_blocks(nbo + 1); DBuf<as_u64> d_first(nbo + 1), d_afirst(nba + 1), d_err(AS_ERRS); DBuf<uint32_t> d_adepth(nba + 1), d_used(nk + 1), d_slotcnt(nmo + 1);
@@ -99,22 +67,22 @@ void assemble_blocks_host(int64_t n_blocks, const pga_rc_block_t *rc_blocks, con
 	DBuf<pga_slice_res_t> d_slices(ni + 1); DBuf<pga_slice_member_t> d_smembers(nk + 1); DBuf<pga_mapvar_res_t> d_res(nr + 1); DBuf<uint64_t> d_msrc(nk + 1);
 	DBuf<char> d_letters(ins_seq_len + p_ins_seq_len + 1); DBuf<pga_topo_node_t> d_nodes(nn + 1);
 	DBuf<AsDesc> d_desc(nmo + 1); DBuf<long long> d_origin(nmo + 1); DBuf<pga_detach_member_t> d_who(nmo + 1);
-	as_up(d_blocks, A.blocks.data(), nbo, st); as_up(d_first, (const as_u64*)A.blk_first.data(), nbo + 1, st);
-	as_up(d_members, members, nmb, st); as_up(d_subs, subs, nbs, st); as_up(d_dels, dels, nbd, st); as_up(d_inss, inss, nbi, st);
+	upload(d_blocks, A.blocks.data(), nbo, st); upload(d_first, (const as_u64*)A.blk_first.data(), nbo + 1, st);
+	upload(d_members, members, nmb, st); upload(d_subs, subs, nbs, st); upload(d_dels, dels, nbd, st); upload(d_inss, inss, nbi, st);
 	if (ins_seq_len) PGA_HIP(hipMemcpyAsync(d_letters.p, ins_seq, ins_seq_len, hipMemcpyHostToDevice, st));
 	if (!A.identity) {
-		as_up(d_afirst, (const as_u64*)A.after_first.data(), nba, st); as_up(d_adepth, A.after_depth.data(), nba, st);
-		as_up(d_slices, slice->slices, ni, st); as_up(d_smembers, slice->members, nk, st); as_up(d_msrc, applied->member_src, nk, st);
-		as_up(d_ssubs, slice->subs, A.slice_tot[0], st); as_up(d_sdels, slice->dels, A.slice_tot[1], st); as_up(d_sinss, slice->inss, A.slice_tot[2], st);
-		as_up(d_res, res, nr, st); as_up(d_psubs, p_subs, A.p_tot[0], st); as_up(d_pdels, p_dels, A.p_tot[1], st); as_up(d_pinss, p_inss, A.p_tot[2], st);
+		upload(d_afirst, (const as_u64*)A.after_first.data(), nba, st); upload(d_adepth, A.after_depth.data(), nba, st);
+		upload(d_slices, slice->slices, ni, st); upload(d_smembers, slice->members, nk, st); upload(d_msrc, applied->member_src, nk, st);
+		upload(d_ssubs, slice->subs, A.slice_tot[0], st); upload(d_sdels, slice->dels, A.slice_tot[1], st); upload(d_sinss, slice->inss, A.slice_tot[2], st);
+		upload(d_res, res, nr, st); upload(d_psubs, p_subs, A.p_tot[0], st); upload(d_pdels, p_dels, A.p_tot[1], st); upload(d_pinss, p_inss, A.p_tot[2], st);
 		if (p_ins_seq_len) PGA_HIP(hipMemcpyAsync(d_letters.p + ins_seq_len, p_ins_seq, p_ins_seq_len, hipMemcpyHostToDevice, st));
-		as_up(d_nodes, applied->nodes, nn, st);
+		upload(d_nodes, applied->nodes, nn, st);
 	}
 	clock.at(1);
 	// ---- the descriptors, who, the two member scans ----
 	d_used.zero(st); d_slotcnt.zero(st);
 	PGA_HIP(hipMemsetAsync(d_err.p, 0xff, AS_ERRS * sizeof(as_u64), st));
-	AsScanBufs b_before, b_out, b_let;
+	TileScanBufs<as_u64> b_before, b_out, b_let;
 	AsDev V;
 	memset(&V, 0, sizeof(V));
 	V.n_out_blocks = nbo; V.n_out_members = nmo; V.n_before_members = nmb; V.n_nodes = nn; V.n_after_blocks = nba; V.ins_seq_len = ins_seq_len; V.p_ins_seq_len = p_ins_seq_len;
@@ -125,23 +93,23 @@ void assemble_blocks_host(int64_t n_blocks, const pga_rc_block_t *rc_blocks, con
 	V.desc = d_desc.p; V.o_members = d_omembers.p; V.origin = d_origin.p;
 	V.nodes = d_nodes.p; V.after_first = d_afirst.p; V.after_depth = d_adepth.p; V.who = d_who.p; V.slot_cnt = d_slotcnt.p; V.err = d_err.p;
 	V.scan[AS_SCAN_BEFORE] = b_before.make(nmb, 3); V.scan[AS_SCAN_OUT] = b_out.make(nmo, 3);
-	as_scan<AS_SCAN_BEFORE>(V, st);
+	tile_scan_launch(V.scan[AS_SCAN_BEFORE], AsBeforeValue{V}, st);
 	hipLaunchKernelGGL(k_assemble_desc, dim3(as_grid(nmo)), dim3(AS_THREADS), 0, st, V);
 	if (who) {
 		hipLaunchKernelGGL(k_assemble_who, dim3(as_grid(nn)), dim3(AS_THREADS), 0, st, V);
 		hipLaunchKernelGGL(k_assemble_who_check, dim3(as_grid(nmo)), dim3(AS_THREADS), 0, st, V);
 	}
-	as_scan<AS_SCAN_OUT>(V, st);
+	tile_scan_launch(V.scan[AS_SCAN_OUT], AsOutValue{V}, st);
 	PGA_HIP(hipGetLastError());
 	// ---- the first wait: nothing behind it runs on input that was not checked ----
 	as_u64 err[AS_ERRS], tot[3];
-	as_fetch(err, (const as_u64*)d_err.p, AS_ERRS, st);
-	for (int q = 0; q < 3; ++q) as_fetch(&tot[q], rm_off(V.scan[AS_SCAN_OUT], q) + nmo, 1, st);
+	fetch(err, (const as_u64*)d_err.p, AS_ERRS, st);
+	for (int q = 0; q < 3; ++q) fetch(&tot[q], ts_off(V.scan[AS_SCAN_OUT], q) + nmo, 1, st);
 	PGA_HIP(sync_stream(st));
 	as_u64 status_k = 0;
 	if (err[AS_E_STATUS] != AS_NONE) {                                        // (the failing path only: which slice member it was)
 		long long o = 0;
-		as_fetch(&o, (const long long*)d_origin.p + err[AS_E_STATUS], 1, st);
+		fetch(&o, (const long long*)d_origin.p + err[AS_E_STATUS], 1, st);
 		PGA_HIP(sync_stream(st));
 		status_k = (as_u64)(-(o + 1));
 	}
@@ -156,11 +124,11 @@ void assemble_blocks_host(int64_t n_blocks, const pga_rc_block_t *rc_blocks, con
 	if (nd_out) hipLaunchKernelGGL(k_assemble_copy<RM_LIST_DEL>, dim3(as_tile_grid(nd_out)), dim3(AS_THREADS), 0, st, V);
 	if (ni_out) hipLaunchKernelGGL(k_assemble_copy<RM_LIST_INS>, dim3(as_tile_grid(ni_out)), dim3(AS_THREADS), 0, st, V);
 	V.scan[AS_SCAN_LETTERS] = b_let.make(ni_out, 1);
-	as_scan<AS_SCAN_LETTERS>(V, st);
+	tile_scan_launch(V.scan[AS_SCAN_LETTERS], AsLetterValue{V}, st);
 	PGA_HIP(hipGetLastError());
 	// ---- the second wait: every insertion lies inside its buffer before a letter is read ----
 	as_u64 n_let = 0;
-	as_fetch(err, (const as_u64*)d_err.p, AS_ERRS, st); as_fetch(&n_let, rm_off(V.scan[AS_SCAN_LETTERS], 0) + ni_out, 1, st);
+	fetch(err, (const as_u64*)d_err.p, AS_ERRS, st); fetch(&n_let, ts_off(V.scan[AS_SCAN_LETTERS], 0) + ni_out, 1, st);
 	PGA_HIP(sync_stream(st));
 	as_report_letters(err);
 	const uint64_t nl_out = n_let;
@@ -171,15 +139,15 @@ void assemble_blocks_host(int64_t n_blocks, const pga_rc_block_t *rc_blocks, con
 	PGA_HIP(hipGetLastError());
 	clock.at(2);
 	// ---- the output ----
-	out->subs = as_host_array<pga_sub_t>(ns_out); out->dels = as_host_array<pga_del_t>(nd_out); out->inss = as_host_array<pga_ins_t>(ni_out);
-	out->ins_seq = as_host_array<char>(nl_out + 1);
-	as_fetch(out->members, (const pga_rc_member_t*)d_omembers.p, nmo, st); as_fetch((long long*)out->origin, (const long long*)d_origin.p, nmo, st);
-	if (who) as_fetch(out->who, (const pga_detach_member_t*)d_who.p, nmo, st);
-	as_fetch(out->subs, (const pga_sub_t*)d_osubs.p, ns_out, st); as_fetch(out->dels, (const pga_del_t*)d_odels.p, nd_out, st);
-	as_fetch(out->inss, (const pga_ins_t*)d_oinss.p, ni_out, st); as_fetch(out->ins_seq, (const char*)d_oseq.p, nl_out, st);
+	out->subs = host_array<pga_sub_t>(ns_out, "pga_assemble_blocks"); out->dels = host_array<pga_del_t>(nd_out, "pga_assemble_blocks"); out->inss = host_array<pga_ins_t>(ni_out, "pga_assemble_blocks");
+	out->ins_seq = host_array<char>(nl_out + 1, "pga_assemble_blocks");
+	fetch(out->members, (const pga_rc_member_t*)d_omembers.p, nmo, st); fetch((long long*)out->origin, (const long long*)d_origin.p, nmo, st);
+	if (who) fetch(out->who, (const pga_detach_member_t*)d_who.p, nmo, st);
+	fetch(out->subs, (const pga_sub_t*)d_osubs.p, ns_out, st); fetch(out->dels, (const pga_del_t*)d_odels.p, nd_out, st);
+	fetch(out->inss, (const pga_ins_t*)d_oinss.p, ni_out, st); fetch(out->ins_seq, (const char*)d_oseq.p, nl_out, st);
 	clock.at(3);
 	PGA_HIP(sync_stream(st));
-	clock.read();
+	clock.read(g_as_ms);
 	out->n_subs = ns_out; out->n_dels = nd_out; out->n_inss = ni_out; out->n_ins_letters = nl_out;
 }
 

@@ -2,7 +2,7 @@
 // reweave.rs:88-93 alignment_insert; the insertion of the merged blocks, graph_merging.rs:156-165; the blocks split_block leaves,
 // reweave.rs:359-401).  No wave intrinsic, atomicAdd / atomicMin only: all of this compiles under hipcc and, with dev/emu/hip_emu.h
 // included first, under g++ -std=c++17 -DPGA_EMU (tests/emu/assemble_emu.cpp runs it against a direct scalar construction).
-// The workgroup scan through LDS, the lookup in scanned offsets and the scan record are pga_remove_idx.h's (rm_block_excl, rm_last_le, RmScan).
+// The scans are the tile scan of pga_tile_scan.h (k_ts_sums / _scan / _offsets, ts_last_le) with the value functors below.
 //
 // A MEMBER is a member of the output, m.  Its DESCRIPTOR says where its three lists come from: the SOURCE (the caller's arrays of the graph
 // before, the sliced lists, the promise results), the three counts and the three first elements there.  A survivor's first elements are the
@@ -20,7 +20,7 @@
 namespace pga {
 
 typedef rm_u64 as_u64;
-constexpr int AS_THREADS = RM_THREADS, AS_ITEMS = RM_ITEMS, AS_TILE = RM_TILE;
+constexpr int AS_THREADS = TS_THREADS, AS_TILE = TS_TILE;
 static_assert(AS_TILE == PGA_ASSEMBLE_TILE, "the header exports the tile of the scans");
 enum { AS_SCAN_BEFORE = 0, AS_SCAN_OUT = 1, AS_SCAN_LETTERS = 2, AS_SCANS = 3 };
 enum { AS_SRC_BEFORE = 0, AS_SRC_SLICE = 1, AS_SRC_PROMISE = 2 };
@@ -51,64 +51,21 @@ struct AsDev {
 	as_u64 *err;                                           // AS_ERRS words
 };
 
-template <int K> __host__ __device__ inline as_u64 as_value(const AsDev &V, int q, as_u64 i);
-template <> __host__ __device__ inline as_u64 as_value<AS_SCAN_BEFORE>(const AsDev &V, int q, as_u64 i)
-{
-	const pga_rc_member_t M = V.members[i];
-	return q == RM_LIST_SUB ? M.n_subs : q == RM_LIST_DEL ? M.n_dels : M.n_inss;
-}
-template <> __host__ __device__ inline as_u64 as_value<AS_SCAN_OUT>(const AsDev &V, int q, as_u64 i) { return V.desc[i].n[q]; }
-template <> __host__ __device__ inline as_u64 as_value<AS_SCAN_LETTERS>(const AsDev &V, int, as_u64 i) { return V.o_inss[i].len; }
+// what a member before, a descriptor and an output insertion are worth in their scans
+struct AsBeforeValue {
+	AsDev V;
+	__host__ __device__ as_u64 operator()(int q, uint64_t i) const
+	{
+		const pga_rc_member_t M = V.members[i];
+		return q == RM_LIST_SUB ? M.n_subs : q == RM_LIST_DEL ? M.n_dels : M.n_inss;
+	}
+};
+struct AsOutValue { AsDev V; __host__ __device__ as_u64 operator()(int q, uint64_t i) const { return V.desc[i].n[q]; } };
+struct AsLetterValue { AsDev V; __host__ __device__ as_u64 operator()(int, uint64_t i) const { return V.o_inss[i].len; } };
 // off + n <= tot, without wrapping
 __host__ __device__ inline bool as_inside(as_u64 off, as_u64 n, as_u64 tot) { return off <= tot && n <= tot - off; }
 
-// ---------------------------------------------------------------- 1. the scans: tile sums, ONE workgroup over them, the offsets (64 bits, two levels)
-template <int K> static __global__ __launch_bounds__(AS_THREADS) void k_assemble_tile_sums(AsDev V)
-{
-	__shared__ as_u64 s[AS_THREADS];
-	const RmScan S = V.scan[K];
-	for (uint32_t t = blockIdx.x; t < S.n_tiles; t += gridDim.x) {
-		const as_u64 i0 = (as_u64)t * AS_TILE + (as_u64)threadIdx.x * AS_ITEMS;
-		for (uint32_t q = 0; q < S.n_q; ++q) {
-			as_u64 v = 0, total;
-			for (int k = 0; k < AS_ITEMS; ++k) if (i0 + k < S.n) v += as_value<K>(V, (int)q, i0 + k);
-			rm_block_excl(v, s, total);
-			if (threadIdx.x == 0) S.tile_sum[(as_u64)q * S.n_tiles + t] = total;
-		}
-	}
-}
-// tile_off[q][t] = what the tiles before t add; tile_off[q][n_tiles] = off[q][n] = the total
-template <int K> static __global__ __launch_bounds__(AS_THREADS) void k_assemble_tile_scan(AsDev V)
-{
-	__shared__ as_u64 s[AS_THREADS];
-	const RmScan S = V.scan[K];
-	for (uint32_t q = 0; q < S.n_q; ++q) {
-		as_u64 run = 0;
-		for (uint32_t t0 = 0; t0 < S.n_tiles; t0 += AS_THREADS) {
-			const uint32_t t = t0 + threadIdx.x;
-			const as_u64 v = t < S.n_tiles ? S.tile_sum[(as_u64)q * S.n_tiles + t] : 0ULL;
-			as_u64 total;
-			const as_u64 before = rm_block_excl(v, s, total);
-			if (t < S.n_tiles) S.tile_off[(as_u64)q * (S.n_tiles + 1) + t] = run + before;
-			run += total;
-		}
-		if (threadIdx.x == 0) { S.tile_off[(as_u64)q * (S.n_tiles + 1) + S.n_tiles] = run; S.off[(as_u64)q * (S.n + 1) + S.n] = run; }
-	}
-}
-template <int K> static __global__ __launch_bounds__(AS_THREADS) void k_assemble_offsets(AsDev V)
-{
-	__shared__ as_u64 s[AS_THREADS];
-	const RmScan S = V.scan[K];
-	for (uint32_t t = blockIdx.x; t < S.n_tiles; t += gridDim.x) {
-		const as_u64 i0 = (as_u64)t * AS_TILE + (as_u64)threadIdx.x * AS_ITEMS;
-		for (uint32_t q = 0; q < S.n_q; ++q) {
-			as_u64 c[AS_ITEMS], v = 0, total;
-			for (int k = 0; k < AS_ITEMS; ++k) { c[k] = i0 + k < S.n ? as_value<K>(V, (int)q, i0 + k) : 0ULL; v += c[k]; }
-			as_u64 at = S.tile_off[(as_u64)q * (S.n_tiles + 1) + t] + rm_block_excl(v, s, total);
-			for (int k = 0; k < AS_ITEMS && i0 + k < S.n; ++k) { S.off[(as_u64)q * (S.n + 1) + i0 + k] = at; at += c[k]; }
-		}
-	}
-}
+// ---------------------------------------------------------------- 1. the scans: pga_tile_scan.h (64 bits, two levels)
 
 // ---------------------------------------------------------------- 2. behind the BEFORE scan: one thread per output member, its descriptor
 // A descriptor that fails a check keeps three empty lists: nothing behind it reads through a value that was refused.
@@ -116,7 +73,7 @@ static __global__ __launch_bounds__(AS_THREADS) void k_assemble_desc(AsDev V)
 {
 	const RmScan S = V.scan[AS_SCAN_BEFORE];
 	for (as_u64 m = (as_u64)blockIdx.x * AS_THREADS + threadIdx.x; m < V.n_out_members; m += (as_u64)gridDim.x * AS_THREADS) {
-		const as_u64 b = rm_last_le(V.blk_first, 0, V.n_out_blocks, m), s = m - V.blk_first[b];
+		const as_u64 b = ts_last_le(V.blk_first, 0, V.n_out_blocks, m), s = m - V.blk_first[b];
 		const AsBlock B = V.blocks[b];
 		AsDesc D = {{0, 0, 0}, {0, 0, 0}, AS_SRC_BEFORE};
 		long long origin = 0;
@@ -124,7 +81,7 @@ static __global__ __launch_bounds__(AS_THREADS) void k_assemble_desc(AsDev V)
 			const as_u64 g = B.src + s;                                            // (below n_before_members: the host held n_members against the depth after)
 			const pga_rc_member_t M = V.members[g];
 			D.n[0] = M.n_subs; D.n[1] = M.n_dels; D.n[2] = M.n_inss;
-			for (int q = 0; q < 3; ++q) D.off[q] = rm_off(S, q)[g];
+			for (int q = 0; q < 3; ++q) D.off[q] = ts_off(S, q)[g];
 			origin = (long long)g;
 		} else {
 			const as_u64 k = V.member_src[B.src + s];
@@ -188,15 +145,15 @@ template <int LIST> static __global__ __launch_bounds__(AS_THREADS) void k_assem
 {
 	__shared__ as_u64 s_rng[2];
 	const RmScan S = V.scan[AS_SCAN_OUT];
-	const as_u64 *out = rm_off(S, LIST);
+	const as_u64 *out = ts_off(S, LIST);
 	const as_u64 n = out[S.n], n_tiles = (n + AS_TILE - 1) / AS_TILE;
 	for (as_u64 t = blockIdx.x; t < n_tiles; t += gridDim.x) {
 		const as_u64 j0 = t * AS_TILE, j1 = j0 + AS_TILE < n ? j0 + AS_TILE : n;
-		if (threadIdx.x < 2) s_rng[threadIdx.x] = rm_last_le(out, 0, S.n, threadIdx.x ? j1 - 1 : j0);
+		if (threadIdx.x < 2) s_rng[threadIdx.x] = ts_last_le(out, 0, S.n, threadIdx.x ? j1 - 1 : j0);
 		__syncthreads();
 		const as_u64 lo = s_rng[0], hi = s_rng[1] + 1;
 		for (as_u64 j = j0 + threadIdx.x; j < j1; j += AS_THREADS) {
-			const as_u64 m = rm_last_le(out, lo, hi, j);
+			const as_u64 m = ts_last_le(out, lo, hi, j);
 			as_copy_one<LIST>(V, j, V.desc[m].src, V.desc[m].off[LIST] + (j - out[m]));
 		}
 		__syncthreads();
@@ -208,15 +165,15 @@ static __global__ __launch_bounds__(AS_THREADS) void k_assemble_letters(AsDev V)
 {
 	__shared__ as_u64 s_rng[2];
 	const RmScan S = V.scan[AS_SCAN_LETTERS];
-	const as_u64 *out = rm_off(S, 0);
+	const as_u64 *out = ts_off(S, 0);
 	const as_u64 n = out[S.n], n_tiles = (n + AS_TILE - 1) / AS_TILE;
 	for (as_u64 t = blockIdx.x; t < n_tiles; t += gridDim.x) {
 		const as_u64 j0 = t * AS_TILE, j1 = j0 + AS_TILE < n ? j0 + AS_TILE : n;
-		if (threadIdx.x < 2) s_rng[threadIdx.x] = rm_last_le(out, 0, S.n, threadIdx.x ? j1 - 1 : j0);
+		if (threadIdx.x < 2) s_rng[threadIdx.x] = ts_last_le(out, 0, S.n, threadIdx.x ? j1 - 1 : j0);
 		__syncthreads();
 		const as_u64 lo = s_rng[0], hi = s_rng[1] + 1;
 		for (as_u64 j = j0 + threadIdx.x; j < j1; j += AS_THREADS) {
-			const as_u64 k = rm_last_le(out, lo, hi, j);
+			const as_u64 k = ts_last_le(out, lo, hi, j);
 			V.o_ins_seq[j] = V.letters[V.o_inss[k].seq_off + (j - out[k])];
 		}
 		__syncthreads();
@@ -226,7 +183,7 @@ static __global__ __launch_bounds__(AS_THREADS) void k_assemble_letters(AsDev V)
 static __global__ __launch_bounds__(AS_THREADS) void k_assemble_seq_off(AsDev V)
 {
 	const RmScan S = V.scan[AS_SCAN_LETTERS];
-	const as_u64 *out = rm_off(S, 0);
+	const as_u64 *out = ts_off(S, 0);
 	for (as_u64 k = (as_u64)blockIdx.x * AS_THREADS + threadIdx.x; k < S.n; k += (as_u64)gridDim.x * AS_THREADS) V.o_inss[k].seq_off = out[k];
 }
 
@@ -394,7 +351,7 @@ static void as_report(const as_u64 *err, const AsTables &A, as_u64 status_k, con
 	if (err[AS_E_SRC_RANGE] != AS_NONE) as_fail("a member_src entry lies outside the slices of its block (member " + at(err[AS_E_SRC_RANGE]) + " after)");
 	if (err[AS_E_SRC_TWICE] != AS_NONE) as_fail("a member_src entry is used twice (member " + at(err[AS_E_SRC_TWICE]) + " after)");
 	if (err[AS_E_STATUS] != AS_NONE) {
-		const as_u64 m = err[AS_E_STATUS], b = rm_last_le(A.blk_first.data(), 0, A.blocks.size(), m);
+		const as_u64 m = err[AS_E_STATUS], b = ts_last_le(A.blk_first.data(), 0, A.blocks.size(), m);
 		const AsBlock &B = A.blocks[b];
 		as_fail("solve_promise failed for a member that the merged block takes: its res[] entry has a status other than 0 (promise " + at(B.promise) + ", member " +
 		        at(status_k - slices[B.ib].member_off) + "; member " + at(m) + " after)");

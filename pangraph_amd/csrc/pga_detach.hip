@@ -16,17 +16,13 @@
 //                     orphan and would, with few orphans, lose to a host core on long sequences (reasoned, not measured).
 // The totals the device summed are compared with the host's before anything is handed out.  The index arithmetic is pga_detach_idx.h.
 #include "pga_common.h"
+#include "pga_graph_host.h"
+#include "pga_wave.h"
 #include "../../include/pga_align.h"
 #include "pga_detach_idx.h"
 
 namespace pga {
 
-__device__ __forceinline__ dt_u64 dt_wave_incl(dt_u64 v, uint32_t lane)
-{
-#pragma unroll
-	for (int d = 1; d < 64; d <<= 1) { const dt_u64 o = __shfl_up(v, d); if ((int)lane >= d) v += o; }
-	return v;
-}
 // workgroup q, ONE wave: off[q][m] = what scan q adds for the members before m; off[q][n_mem] = the total
 __global__ __launch_bounds__(64) void k_detach_scan(DtDev V)
 {
@@ -36,20 +32,14 @@ __global__ __launch_bounds__(64) void k_detach_scan(DtDev V)
 	dt_u64 run = 0;
 	for (uint64_t c0 = 0; c0 < V.n_mem; c0 += 64) {
 		const uint64_t m = c0 + lane;
-		const dt_u64 v = m < V.n_mem ? dt_scan_value(V.members[m], V.unal[m], q) : 0ULL, in = dt_wave_incl(v, lane);
+		const dt_u64 v = m < V.n_mem ? dt_scan_value(V.members[m], V.unal[m], q) : 0ULL, in = wave_incl_u64(v, lane);
 		if (m < V.n_mem) off[m] = run + in - v;
 		run += __shfl(in, 63);
 	}
 	if (lane == 0) off[V.n_mem] = run;
 }
 
-template <class T> static T *dt_host_array(uint64_t n)
-{
-	T *p = (T*)calloc((size_t)(n ? n : 1), sizeof(T));
-	if (!p) throw std::runtime_error("pga_detach_unaligned: out of host memory");
-	return p;
-}
-static unsigned dt_grid(uint64_t items, uint64_t per_block) { return (unsigned)std::min<uint64_t>(std::max<uint64_t>((items + per_block - 1) / per_block, 1), 1u << 16); }
+static unsigned dt_grid(uint64_t items, uint64_t per_block) { return grid_for(items, per_block, 1u << 16); }
 
 void detach_unaligned_host(int64_t n_blocks, const pga_rc_block_t *blocks, const pga_rc_member_t *members, const pga_sub_t *subs, const pga_del_t *dels, const pga_ins_t *inss,
                            const char *ins_seq, const pga_detach_member_t *who, pga_detach_out_t *out)
@@ -62,12 +52,12 @@ void detach_unaligned_host(int64_t n_blocks, const pga_rc_block_t *blocks, const
 	dt_build_tables(G, who, range_threads(), T);
 	const uint64_t n_mem = G.n_mem, n_orph = T.orphans.size(), n_jobs = T.rows.jobs.size();
 	out->n_blocks = n_blocks + (int64_t)n_orph; out->n_orphans = (int64_t)n_orph;
-	out->blocks = dt_host_array<pga_rc_block_t>((uint64_t)out->n_blocks);
-	out->members = dt_host_array<pga_rc_member_t>(n_mem);
-	out->subs = dt_host_array<pga_sub_t>(T.tot[DT_SUB]); out->dels = dt_host_array<pga_del_t>(T.tot[DT_DEL]); out->inss = dt_host_array<pga_ins_t>(T.tot[DT_INS]);
-	out->member_map = dt_host_array<int64_t>(n_mem);
+	out->blocks = host_array<pga_rc_block_t>((uint64_t)out->n_blocks, "pga_detach_unaligned");
+	out->members = host_array<pga_rc_member_t>(n_mem, "pga_detach_unaligned");
+	out->subs = host_array<pga_sub_t>(T.tot[DT_SUB], "pga_detach_unaligned"); out->dels = host_array<pga_del_t>(T.tot[DT_DEL], "pga_detach_unaligned"); out->inss = host_array<pga_ins_t>(T.tot[DT_INS], "pga_detach_unaligned");
+	out->member_map = host_array<int64_t>(n_mem, "pga_detach_unaligned");
 	const uint64_t cons_bytes = T.rows.units * ROW_LETTERS;
-	if (n_orph) { out->orphans = dt_host_array<pga_detach_orphan_t>(n_orph); out->cons = dt_host_array<char>(cons_bytes + 1); }
+	if (n_orph) { out->orphans = host_array<pga_detach_orphan_t>(n_orph, "pga_detach_unaligned"); out->cons = host_array<char>(cons_bytes + 1, "pga_detach_unaligned"); }
 	for (int64_t b = 0; b < n_blocks; ++b) out->blocks[b] = pga_rc_block_t{blocks[b].consensus, blocks[b].cons_len, T.kept_in[b]};
 	for (uint64_t k = 0; k < n_orph; ++k) out->blocks[n_blocks + k] = pga_rc_block_t{out->cons + T.cons_off[k], T.len[k], 1u};
 	if (n_mem == 0) return;                                                  // (no member: nothing to decide, nothing to pack)

@@ -1,7 +1,7 @@
 // pga_detach_idx.h -- the index arithmetic of pga_detach.hip (detach_unaligned.rs:24-114 over Edit::aligned_count, edits.rs:439-442): the
 // member decision, what the offsets sum, the pack kernel, and the host side (the same decision, the orphans' rows, the block id).  None of it
 // uses a wave intrinsic, so all of this compiles under hipcc and, with dev/emu/hip_emu.h included first, under g++ -std=c++17 -DPGA_EMU
-// (tests/emu/detach_emu.cpp runs it against a direct scalar construction).  The one-wave scans of pga_detach.hip are not in here.
+// (tests/emu/detach_emu.cpp runs it against a direct scalar construction).  The one-wave scans of pga_detach.hip (wave_incl_u64 of pga_wave.h) are not in here; XXH64 is pga_xxh64.h.
 //
 // An input member m is KEPT or UNALIGNED: unaligned iff the 64-bit sum of its deletion lengths reaches its block's cons_len (a block with
 // cons_len == 0: every member).  Five quantities are summed over the members in input order (dt_scan_value), exclusive:
@@ -11,6 +11,7 @@
 #pragma once
 #include "../../include/pga_align.h"
 #include "pga_rows.h"
+#include "pga_xxh64.h"
 #include <algorithm>
 
 namespace pga {
@@ -93,35 +94,13 @@ __global__ __launch_bounds__(DT_THREADS) void k_detach_pack(DtDev V, pga_rc_memb
 }
 
 // ---------------------------------------------------------------- host side
-// XXH64 (seed 0 in utils/id.rs) of n bytes
-static inline uint64_t dt_rol(uint64_t x, int r) { return (x << r) | (x >> (64 - r)); }
-static inline uint64_t dt_rd64(const uint8_t *p) { uint64_t v = 0; for (int i = 7; i >= 0; --i) v = v << 8 | p[i]; return v; }
-static uint64_t dt_xxh64(const uint8_t *p, uint64_t n, uint64_t seed)
-{
-	const uint64_t P1 = 0x9E3779B185EBCA87ULL, P2 = 0xC2B2AE3D27D4EB4FULL, P3 = 0x165667B19E3779F9ULL, P4 = 0x85EBCA77C2B2AE63ULL, P5 = 0x27D4EB2F165667C5ULL;
-	auto round = [&](uint64_t acc, uint64_t in) { return dt_rol(acc + in * P2, 31) * P1; };
-	const uint8_t *end = p + n;
-	uint64_t h;
-	if (n >= 32) {
-		uint64_t v[4] = {seed + P1 + P2, seed + P2, seed, seed - P1};
-		for (; end - p >= 32; p += 32) for (int i = 0; i < 4; ++i) v[i] = round(v[i], dt_rd64(p + 8 * i));
-		h = dt_rol(v[0], 1) + dt_rol(v[1], 7) + dt_rol(v[2], 12) + dt_rol(v[3], 18);
-		for (int i = 0; i < 4; ++i) h = (h ^ round(0, v[i])) * P1 + P4;
-	} else h = seed + P5;
-	h += n;
-	for (; end - p >= 8; p += 8) h = dt_rol(h ^ round(0, dt_rd64(p)), 27) * P1 + P4;
-	if (end - p >= 4) { const uint64_t w = (uint64_t)p[0] | (uint64_t)p[1] << 8 | (uint64_t)p[2] << 16 | (uint64_t)p[3] << 24; h = dt_rol(h ^ (w * P1), 23) * P2 + P3; p += 4; }
-	for (; p < end; ++p) h = dt_rol(h ^ (*p * P5), 11) * P1;
-	h ^= h >> 33; h *= P2; h ^= h >> 29; h *= P3; h ^= h >> 32;
-	return h;
-}
 // id((node_id, &seq)): node_id and the length as little-endian u64, then the letters; buf is scratch
 static uint64_t dt_block_id(uint64_t node_id, const char *seq, uint64_t len, std::vector<uint8_t> &buf)
 {
 	buf.resize((size_t)(16 + len));
 	for (int i = 0; i < 8; ++i) { buf[i] = (uint8_t)(node_id >> (8 * i)); buf[8 + i] = (uint8_t)(len >> (8 * i)); }
 	if (len) memcpy(buf.data() + 16, seq, (size_t)len);
-	return dt_xxh64(buf.data(), 16 + len, 0);
+	return xxh64_bytes(buf.data(), 16 + len, 0);
 }
 
 // what the host works out before anything is launched: the decision for every member (so that runs are built for orphans only and

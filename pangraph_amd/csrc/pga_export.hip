@@ -16,6 +16,7 @@
 //                           library holds no row buffer.
 // Neither knob changes a result.
 #include "pga_common.h"
+#include "pga_graph_host.h"
 #include "../../include/pga_align.h"
 #include "pga_rows.h"
 
@@ -23,20 +24,7 @@ namespace pga {
 
 constexpr int EX_BUSY_FAMILY = 16;                           // pga_busy_end (include/pga_align.h): the first family behind those of pga_stats_t
 
-// an environment knob in KB, read at every call
-static uint64_t ex_knob_kb(const std::string &who, const char *name, uint64_t dflt, uint64_t multiple)
-{
-	const char *e = getenv(name);
-	if (!e || !*e) return dflt;
-	char *end = nullptr;
-	const long long v = strtoll(e, &end, 10);
-	if (*end || v < (long long)multiple || v > (1LL << 31) || (uint64_t)v % multiple)
-		throw std::runtime_error(who + ": " + name + " must be a whole number of KB, a multiple of " + std::to_string(multiple) + " (got '" + e + "')");
-	return (uint64_t)v;
-}
-
 namespace {
-struct ExEvent { hipEvent_t e = nullptr; ExEvent() { PGA_HIP(hipEventCreate(&e)); } ~ExEvent() { (void)hipEventDestroy(e); } };
 struct ExPin { char *p = nullptr; uint64_t cap = 0; ~ExPin() { pin_free(p); } };
 }
 
@@ -59,8 +47,8 @@ static void export_rows(const std::string &who, const RowGraph &G, uint64_t n_ro
 		for (uint64_t q = piece_first[r]; q < piece_first[r + 1]; ++q) { l += G.mem_len[pieces[q].member]; if (l > (1ULL << 31)) fail("row over 2^31 letters (row " + std::to_string(r) + ")"); }
 		res[r].status = 0; res[r].pad = 0; res[r].len = l;
 	}
-	const uint64_t tile_units = ex_knob_kb(who, "PGA_EXPORT_TILE_KB", 16384, 4) * 1024 / ROW_LETTERS;
-	const uint64_t runs_cap = ex_knob_kb(who, "PGA_EXPORT_RUNS_KB", 262144, 1) * 1024 / sizeof(RowRun);
+	const uint64_t tile_units = export_tile_bytes(fail) / ROW_LETTERS;
+	const uint64_t runs_cap = knob_kb(fail, "PGA_EXPORT_RUNS_KB", 262144, 1) * 1024 / sizeof(RowRun);
 	const uint32_t gap_flag = G.aligned ? 0u : ROW_GAP;
 
 	// (declared before the streams: the streams are drained first when the scope is left, by a throw too)
@@ -70,7 +58,7 @@ static void export_rows(const std::string &who, const RowGraph &G, uint64_t n_ro
 	RowTable T; PreparedEdit P; std::vector<PrSeg> segs_scratch;
 	std::vector<pga_export_seg_t> segs;
 	std::vector<uint32_t> flags;
-	ExEvent ev_ka[2], ev_kb[2], ev_c[2];                                  // per tile buffer: before and behind its kernel, behind its copy
+	Event ev_ka[2], ev_kb[2], ev_c[2];                                  // per tile buffer: before and behind its kernel, behind its copy
 	StreamLease s_kern, s_copy;                                           // (release drains the stream)
 	const hipStream_t sk = s_kern.s, sc = s_copy.s;
 

@@ -16,62 +16,16 @@
 // The kernels and the host tables are pga_gfa_idx.h (no wave intrinsic: tests/emu/gfa_emu.cpp runs them on the host).
 // All arithmetic is integer; concurrent stores to one word store the same value, so the result does not depend on the launch geometry.
 #include "pga_common.h"
+#include "pga_graph_host.h"
 #include "../../include/pga_align.h"
 #include "pga_gfa_idx.h"
-#include <chrono>
-#include <rocprim/rocprim.hpp>
 
 namespace pga {
 
-template <class T> static T *gf_host_array(uint64_t n)
-{
-	T *p = (T*)calloc((size_t)(n ? n : 1), sizeof(T));
-	if (!p) gf_fail("out of host memory");
-	return p;
-}
-static unsigned gf_grid(uint64_t items) { return (unsigned)std::min<uint64_t>(std::max<uint64_t>((items + GF_THREADS - 1) / GF_THREADS, 1), 2048); }
-template <class T> static void gf_up(DBuf<T> &d, const T *h, uint64_t n, hipStream_t st) { if (n) PGA_HIP(hipMemcpyAsync(d.p, h, n * sizeof(T), hipMemcpyHostToDevice, st)); }
-template <class T> static void gf_fetch(T *dst, const T *src, uint64_t n, hipStream_t st) { if (n) PGA_HIP(hipMemcpyAsync(dst, src, n * sizeof(T), hipMemcpyDeviceToHost, st)); }
-static void gf_sort(const gf_u64 *in, gf_u64 *out, uint64_t n, hipStream_t st)
-{
-	size_t tb = 0;
-	PGA_HIP(rocprim::radix_sort_keys(nullptr, tb, in, out, n, 0, 64, st));
-	DBuf<uint8_t> tmp(tb + 16);
-	PGA_HIP(rocprim::radix_sort_keys(tmp.p, tb, in, out, n, 0, 64, st));
-}
-struct GfScanBufs {
-	DBuf<gf_u64> tile_sum, tile_off, off;
-	GfScan make(const gf_u64 *val, uint64_t n)
-	{
-		const uint32_t n_tiles = (uint32_t)((n + GF_TILE - 1) / GF_TILE);
-		tile_sum.alloc(n_tiles + 1); tile_off.alloc(n_tiles + 1); off.alloc(n + 1);
-		return GfScan{n, n_tiles, 0, val, tile_sum.p, tile_off.p, off.p};
-	}
-};
-static void gf_scan(const GfScan &S, hipStream_t st)
-{
-	if (S.n_tiles) hipLaunchKernelGGL(k_gfa_tile_sums, dim3(std::min<uint32_t>(S.n_tiles, 2048u)), dim3(GF_THREADS), 0, st, S);
-	hipLaunchKernelGGL(k_gfa_tile_scan, dim3(1), dim3(GF_THREADS), 0, st, S);
-	if (S.n_tiles) hipLaunchKernelGGL(k_gfa_offsets, dim3(std::min<uint32_t>(S.n_tiles, 2048u)), dim3(GF_THREADS), 0, st, S);
-}
-// PGA_EXPORT_TILE_KB as pga_export.hip reads it: at every call
-static uint64_t gf_tile_bytes()
-{
-	const char *e = getenv("PGA_EXPORT_TILE_KB");
-	if (!e || !*e) return 16384ULL * 1024;
-	char *end = nullptr;
-	const long long v = strtoll(e, &end, 10);
-	if (*end || v < 4 || v > (1LL << 31) || v % 4) gf_fail(std::string("PGA_EXPORT_TILE_KB must be a whole number of KB, a multiple of 4 (got '") + e + "')");
-	return (uint64_t)v * 1024;
-}
+static unsigned gf_grid(uint64_t items) { return grid_for(items, GF_THREADS, 2048); }
 
-namespace {
-struct GfEvent { hipEvent_t e = nullptr; GfEvent() { PGA_HIP(hipEventCreate(&e)); } ~GfEvent() { (void)hipEventDestroy(e); } };
-struct GfPin { char *p = nullptr; ~GfPin() { pin_free(p); } };
-}
 static thread_local double g_gf_ms[4] = {0, 0, 0, 0};
 void gfa_last_ms(double *ms) { for (int i = 0; i < 4; ++i) ms[i] = g_gf_ms[i]; }
-static double gf_now() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
 
 static const char GF_HEADER[] = "H\tVN:Z:1.0\n";
 
@@ -81,9 +35,9 @@ void export_gfa_host(int64_t n_blocks, const pga_topo_block_t *blocks, int64_t n
 {
 	TpTables T;
 	gf_validate(n_blocks, blocks, n_paths, paths, n_nodes, nodes, cons, p, flags, T);
-	const uint64_t tile_bytes = gf_tile_bytes();
-	out->segments = gf_host_array<pga_gfa_segment_t>(0); out->links = gf_host_array<pga_topo_edge_t>(0); out->paths = gf_host_array<pga_gfa_path_t>(0);
-	if (flags & PGA_GFA_STEPS) out->steps = gf_host_array<pga_gfa_step_t>(0);
+	const uint64_t tile_bytes = export_tile_bytes(gf_fail);
+	out->segments = host_array<pga_gfa_segment_t>(0, "pga_export_gfa"); out->links = host_array<pga_topo_edge_t>(0, "pga_export_gfa"); out->paths = host_array<pga_gfa_path_t>(0, "pga_export_gfa");
+	if (flags & PGA_GFA_STEPS) out->steps = host_array<pga_gfa_step_t>(0, "pga_export_gfa");
 	out->n_bytes = sizeof(GF_HEADER) - 1;
 	auto header_only = [&]() { if (sink && sink(ctx, GF_HEADER, (int64_t)sizeof(GF_HEADER) - 1) != 0) gf_fail("sink stopped the export"); };
 	if (n_paths == 0 || n_nodes == 0) { header_only(); return; }
@@ -91,7 +45,7 @@ void export_gfa_host(int64_t n_blocks, const pga_topo_block_t *blocks, int64_t n
 
 	// (declared before the streams: the streams are drained first when the scope is left, by a throw too)
 	DBuf<char> d_tile[2];
-	GfPin pin[2];
+	PinBlock pin[2];
 	DBuf<pga_topo_node_t> d_nodes(nn + 1); DBuf<pga_topo_path_t> d_paths(np + 1); DBuf<pga_topo_block_t> d_blocks(nb + 1);
 	DBuf<uint32_t> d_depth(nb + 1), d_first(nb + 2), d_pathof(nn + 1), d_cnts(T.n_slots + nb + 1), d_terr(TP_ERRS), d_flags(2 * nb + 1), d_steppath(nn + 1);
 	DBuf<uint32_t> d_head(nn + 1), d_hoff(nn + 1), d_rstart(nn + 1);
@@ -99,15 +53,15 @@ void export_gfa_host(int64_t n_blocks, const pga_topo_block_t *blocks, int64_t n
 	DBuf<gf_u64> d_keep(nn + 1), d_psteps(2 * np + 1), d_len, d_rowoff;
 	DBuf<pga_gfa_step_t> d_steps(nn + 1); DBuf<pga_topo_edge_t> d_links(nn + 1);
 	DBuf<pga_gfa_segment_t> d_segs; DBuf<GfRow> d_rows;
-	GfScanBufs b_keep, b_items;
-	GfEvent ev_0, ev_1, ev_ka[2], ev_kb[2], ev_c[2];
+	TileScanBufs<gf_u64> b_keep, b_items;
+	Event ev_0, ev_1, ev_ka[2], ev_kb[2], ev_c[2];
 	StreamLease s_kern, s_copy;
 	const hipStream_t st = s_kern.s, sc = s_copy.s;
 
 	// ---- the uploads, the checks of the graph as pga_plan_simplify makes them ----
 	PGA_HIP(hipEventRecord(ev_0.e, st));
-	gf_up(d_nodes, nodes, nn, st); gf_up(d_paths, paths, np, st); gf_up(d_blocks, blocks, nb, st);
-	gf_up(d_depth, T.depth.data(), nb, st); gf_up(d_first, T.slot_first.data(), nb + 1, st);
+	upload(d_nodes, nodes, nn, st); upload(d_paths, paths, np, st); upload(d_blocks, blocks, nb, st);
+	upload(d_depth, T.depth.data(), nb, st); upload(d_first, T.slot_first.data(), nb + 1, st);
 	d_cnts.zero(st); d_flags.zero(st);
 	PGA_HIP(hipMemsetAsync(d_terr.p, 0xff, TP_ERRS * sizeof(uint32_t), st));
 	PGA_HIP(hipMemsetAsync(d_k0.p, 0xff, (nn + 1) * sizeof(tp_u64), st));
@@ -120,7 +74,7 @@ void export_gfa_host(int64_t n_blocks, const pga_topo_block_t *blocks, int64_t n
 	memset(&V, 0, sizeof(V));
 	V.n_nodes = nn; V.n_paths = np; V.n_blocks = nb; V.nodes = d_nodes.p; V.paths = d_paths.p; V.blocks = d_blocks.p; V.path_of = d_pathof.p; V.prm = *p;
 	V.dup = d_flags.p; V.used = d_flags.p + nb; V.keep = d_keep.p; V.steps = d_steps.p; V.step_path = d_steppath.p; V.path_steps = d_psteps.p; V.links = d_links.p;
-	const GfScan s_keep = b_keep.make(d_keep.p, nn);
+	const GfScan s_keep = b_keep.make(nn, 1);
 	V.koff = s_keep.off;
 	const unsigned g_pos = gf_grid(nn + 1);
 	hipLaunchKernelGGL(k_topo_keys, dim3(g_pos), dim3(TP_THREADS), 0, st, K);
@@ -128,41 +82,36 @@ void export_gfa_host(int64_t n_blocks, const pga_topo_block_t *blocks, int64_t n
 	// ---- duplication, the filter, the steps ----
 	V.dkey = d_key.p; V.dskey = d_k1.p;                                     // (the edge keys of k_topo_keys are not used: their buffer serves)
 	hipLaunchKernelGGL(k_gfa_dupkeys, dim3(g_pos), dim3(GF_THREADS), 0, st, V);
-	gf_sort(d_key.p, d_k1.p, nn, st);
+	radix_sort_keys(d_key.p, d_k1.p, nn, 64, st);
 	hipLaunchKernelGGL(k_gfa_dupflags, dim3(g_pos), dim3(GF_THREADS), 0, st, V);
 	hipLaunchKernelGGL(k_gfa_keep, dim3(g_pos), dim3(GF_THREADS), 0, st, V);
-	gf_scan(s_keep, st);
+	tile_scan_launch(s_keep, TsArray<gf_u64>{d_keep.p}, st);
 	hipLaunchKernelGGL(k_gfa_steps, dim3(g_pos), dim3(GF_THREADS), 0, st, V);
 	hipLaunchKernelGGL(k_gfa_path_steps, dim3(gf_grid(np)), dim3(GF_THREADS), 0, st, V);
 	// ---- the links: keys in d_k0 (all-ones where a step has no successor, and behind the last step), sorted into d_k1 ----
 	V.lkey = d_k0.p; V.lskey = d_k1.p; V.head_off = d_hoff.p; V.run_start = d_rstart.p;
 	K.skey = d_k1.p; K.head = d_head.p; K.head_off = d_hoff.p; K.run_start = d_rstart.p;
 	hipLaunchKernelGGL(k_gfa_link_keys, dim3(g_pos), dim3(GF_THREADS), 0, st, V);
-	gf_sort(d_k0.p, d_k1.p, nn, st);
+	radix_sort_keys(d_k0.p, d_k1.p, nn, 64, st);
 	hipLaunchKernelGGL(k_topo_heads, dim3(g_pos), dim3(TP_THREADS), 0, st, K);
-	{
-		size_t tb = 0;
-		PGA_HIP(rocprim::exclusive_scan(nullptr, tb, d_head.p, d_hoff.p, 0u, nn + 1, rocprim::plus<uint32_t>(), st));
-		DBuf<uint8_t> tmp(tb + 16);
-		PGA_HIP(rocprim::exclusive_scan(tmp.p, tb, d_head.p, d_hoff.p, 0u, nn + 1, rocprim::plus<uint32_t>(), st));
-	}
+	excl_scan(d_head.p, d_hoff.p, nn + 1, st);
 	hipLaunchKernelGGL(k_topo_runs, dim3(g_pos), dim3(TP_THREADS), 0, st, K);
 	hipLaunchKernelGGL(k_gfa_links, dim3(g_pos), dim3(GF_THREADS), 0, st, V);
 	PGA_HIP(hipGetLastError());
 	// ---- the first wait: nothing behind it runs on input that was not checked ----
 	uint32_t terr[TP_ERRS], n_runs = 0;
 	gf_u64 n_steps = 0;
-	gf_fetch(terr, (const uint32_t*)d_terr.p, TP_ERRS, st); gf_fetch(&n_runs, (const uint32_t*)d_hoff.p + nn, 1, st); gf_fetch(&n_steps, (const gf_u64*)s_keep.off + nn, 1, st);
+	fetch(terr, (const uint32_t*)d_terr.p, TP_ERRS, st); fetch(&n_runs, (const uint32_t*)d_hoff.p + nn, 1, st); fetch(&n_steps, (const gf_u64*)s_keep.off + nn, 1, st);
 	PGA_HIP(sync_stream(st));
 	gf_report(terr);
 	if (n_steps > nn || n_runs > n_steps) gf_fail("internal: the device counted more steps than positions, or more links than steps");
 	const uint64_t n_links = n_runs;
 	std::vector<uint32_t> h_flags(2 * nb);
 	std::vector<gf_u64> h_psteps(2 * np);
-	free(out->links); out->links = nullptr; out->links = gf_host_array<pga_topo_edge_t>(n_links);
-	if (flags & PGA_GFA_STEPS) { free(out->steps); out->steps = nullptr; out->steps = gf_host_array<pga_gfa_step_t>(n_steps); gf_fetch(out->steps, (const pga_gfa_step_t*)d_steps.p, n_steps, st); }
-	gf_fetch(h_flags.data(), (const uint32_t*)d_flags.p, 2 * nb, st); gf_fetch(h_psteps.data(), (const gf_u64*)d_psteps.p, 2 * np, st);
-	gf_fetch(out->links, (const pga_topo_edge_t*)d_links.p, n_links, st);
+	free(out->links); out->links = nullptr; out->links = host_array<pga_topo_edge_t>(n_links, "pga_export_gfa");
+	if (flags & PGA_GFA_STEPS) { free(out->steps); out->steps = nullptr; out->steps = host_array<pga_gfa_step_t>(n_steps, "pga_export_gfa"); fetch(out->steps, (const pga_gfa_step_t*)d_steps.p, n_steps, st); }
+	fetch(h_flags.data(), (const uint32_t*)d_flags.p, 2 * nb, st); fetch(h_psteps.data(), (const gf_u64*)d_psteps.p, 2 * np, st);
+	fetch(out->links, (const pga_topo_edge_t*)d_links.p, n_links, st);
 	PGA_HIP(sync_stream(st));
 	GfTables G;
 	gf_tables(n_blocks, blocks, n_paths, paths, cons, names, name_len, *p, h_flags.data() + nb, h_flags.data(), h_psteps.data(), n_steps, n_links, G);
@@ -172,26 +121,26 @@ void export_gfa_host(int64_t n_blocks, const pga_topo_block_t *blocks, int64_t n
 	// ---- the layout ----
 	const uint64_t n_items = 4 + n_seg + n_links + n_steps + 2 * n_rows;
 	d_segs.alloc(n_seg + 1); d_rows.alloc(n_rows + 1); d_len.alloc(n_items + 1); d_rowoff.alloc(n_rows + 1);
-	gf_up(d_segs, G.segs.data(), n_seg, st); gf_up(d_rows, G.rows.data(), n_rows, st);
-	const GfScan s_items = b_items.make(d_len.p, n_items);
+	upload(d_segs, G.segs.data(), n_seg, st); upload(d_rows, G.rows.data(), n_rows, st);
+	const GfScan s_items = b_items.make(n_items, 1);
 	V.n_seg = n_seg; V.n_links = n_links; V.n_rows = n_rows; V.n_steps = n_steps; V.n_items = n_items;
 	V.segs = d_segs.p; V.rows = d_rows.p; V.len = d_len.p; V.off = s_items.off; V.row_off = d_rowoff.p;
 	hipLaunchKernelGGL(k_gfa_lens, dim3(gf_grid(n_items)), dim3(GF_THREADS), 0, st, V);
-	gf_scan(s_items, st);
+	tile_scan_launch(s_items, TsArray<gf_u64>{d_len.p}, st);
 	hipLaunchKernelGGL(k_gfa_row_off, dim3(gf_grid(n_rows)), dim3(GF_THREADS), 0, st, V);
 	PGA_HIP(hipGetLastError());
 	// ---- the second wait: the length of the file, where every S and P line starts ----
 	std::vector<gf_u64> h_segoff(n_seg), h_rowoff(n_rows);
 	gf_u64 n_bytes = 0;
-	gf_fetch(&n_bytes, (const gf_u64*)s_items.off + n_items, 1, st);
-	gf_fetch(h_segoff.data(), (const gf_u64*)s_items.off + 2, n_seg, st); gf_fetch(h_rowoff.data(), (const gf_u64*)d_rowoff.p, n_rows, st);
+	fetch(&n_bytes, (const gf_u64*)s_items.off + n_items, 1, st);
+	fetch(h_segoff.data(), (const gf_u64*)s_items.off + 2, n_seg, st); fetch(h_rowoff.data(), (const gf_u64*)d_rowoff.p, n_rows, st);
 	PGA_HIP(hipEventRecord(ev_1.e, st));
 	PGA_HIP(sync_stream(st));
 	if (n_bytes >= (1ULL << 63)) gf_fail("a file of 2^63 bytes or more");
 	for (uint64_t k = 0; k < n_seg; ++k) G.segs[k].byte_off = h_segoff[k];
 	for (uint64_t k = 0; k < n_rows; ++k) G.paths[k].byte_off = h_rowoff[k];
-	free(out->segments); out->segments = nullptr; out->segments = gf_host_array<pga_gfa_segment_t>(n_seg);
-	free(out->paths); out->paths = nullptr; out->paths = gf_host_array<pga_gfa_path_t>(n_rows);
+	free(out->segments); out->segments = nullptr; out->segments = host_array<pga_gfa_segment_t>(n_seg, "pga_export_gfa");
+	free(out->paths); out->paths = nullptr; out->paths = host_array<pga_gfa_path_t>(n_rows, "pga_export_gfa");
 	std::copy(G.segs.begin(), G.segs.end(), out->segments); std::copy(G.paths.begin(), G.paths.end(), out->paths);
 	out->n_segments = (int64_t)n_seg; out->n_paths = (int64_t)n_rows; out->n_bytes = n_bytes;
 	{ float ms = 0; PGA_HIP(hipEventElapsedTime(&ms, ev_0.e, ev_1.e)); g_gf_ms[0] = ms; g_gf_ms[1] = g_gf_ms[2] = g_gf_ms[3] = 0; }
@@ -214,11 +163,11 @@ void export_gfa_host(int64_t n_blocks, const pga_topo_block_t *blocks, int64_t n
 	double ms_kern = 0, ms_fill = 0, ms_sink = 0;
 	auto deliver = [&](uint64_t t) {                                        // tile t lies in its pinned block: the host's letters, then the sink
 		gf_u64 a, z; span(t, a, z);
-		const double c0 = gf_now();
+		const double c0 = now_ms();
 		gf_host_fill(G, blocks, cons, names, p->include_sequences != 0, pin[t & 1].p, a, z, si, pi);
-		const double c1 = gf_now();
+		const double c1 = now_ms();
 		const int rc = sink(ctx, pin[t & 1].p, (int64_t)(z - a));
-		ms_fill += c1 - c0; ms_sink += gf_now() - c1;
+		ms_fill += c1 - c0; ms_sink += now_ms() - c1;
 		if (rc != 0) {
 			(void)hipStreamSynchronize(st); (void)hipStreamSynchronize(sc);     // drain what is in flight: no further sink call
 			gf_fail("sink stopped the export");

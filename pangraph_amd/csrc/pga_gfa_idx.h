@@ -15,7 +15,7 @@
 //   the head of path k is path item rows[k].step_off + 2 k.
 // gf_emit() writes an item through a WINDOW [t0, t1) of the file: a byte inside it is stored, one outside only counted.  With an empty
 // window it gives the item's length (k_gfa_lens), so the layout and the text cannot disagree; a 64-bit scan over the lengths gives every
-// item its file offset; k_gfa_tile writes the items that intersect a tile, an item cut by a tile edge in two parts by two launches.
+// item its file offset (the tile scan of pga_tile_scan.h); k_gfa_tile writes the items that intersect a tile, an item cut by a tile edge in two parts by two launches.
 // Consensus letters and path names are skipped: the host copies them into the tile from the caller's buffers (gf_host_fill).
 #pragma once
 #include "pga_topo_idx.h"
@@ -23,11 +23,10 @@
 namespace pga {
 
 typedef unsigned long long gf_u64;
-constexpr int GF_THREADS = TP_THREADS, GF_ITEMS = TP_ITEMS, GF_TILE = TP_TILE;
+constexpr int GF_THREADS = TS_THREADS, GF_TILE = TS_TILE;
 enum { GF_K_HEADER = 0, GF_K_CBLOCKS, GF_K_SEG, GF_K_CEDGES, GF_K_LINK, GF_K_CPATHS, GF_K_HEAD, GF_K_STEP, GF_K_TAIL };
 
-// one scan: off[i] = the sum of val[0 .. i), off[n] the total; tile_sum: n_tiles entries, tile_off: n_tiles + 1
-struct GfScan { gf_u64 n; uint32_t n_tiles, pad; const gf_u64 *val; gf_u64 *tile_sum, *tile_off, *off; };
+typedef TileScan<gf_u64> GfScan;           // pga_tile_scan.h, one quantity: off[i] = the sum of val[0 .. i) of a TsArray, off[n] the total
 struct GfRow { gf_u64 step_off; uint32_t n_steps, name_len; int32_t circular, pad; };   // an emitted path
 struct GfDev {
 	uint64_t n_nodes, n_paths, n_blocks;
@@ -53,12 +52,6 @@ struct GfDev {
 	char *tile; gf_u64 t0, t1;
 };
 
-// the last index x in [lo, hi) with off[x] <= j, given off[lo] <= j < off[hi] (empty items share their offset with the item behind them)
-__host__ __device__ inline gf_u64 gf_last_le(const gf_u64 *off, gf_u64 lo, gf_u64 hi, gf_u64 j)
-{
-	while (hi - lo > 1) { const gf_u64 mid = (lo + hi) >> 1; if (off[mid] <= j) lo = mid; else hi = mid; }
-	return lo;
-}
 // the number of decimal digits: comparisons against the powers of ten, no division
 __host__ __device__ inline uint32_t gf_width(gf_u64 v)
 {
@@ -166,60 +159,6 @@ static __global__ __launch_bounds__(GF_THREADS) void k_gfa_keep(GfDev V)
 	}
 }
 
-// ---------------------------------------------------------------- the scan: tile sums, ONE workgroup over them, the offsets
-__device__ inline gf_u64 gf_block_excl(gf_u64 v, gf_u64 *s, gf_u64 &total)
-{
-	const uint32_t t = threadIdx.x;
-	s[t] = v;
-	__syncthreads();
-	for (uint32_t d = 1; d < (uint32_t)GF_THREADS; d <<= 1) {
-		const gf_u64 x = t >= d ? s[t - d] : 0ULL;
-		__syncthreads();
-		s[t] += x;
-		__syncthreads();
-	}
-	total = s[GF_THREADS - 1];
-	const gf_u64 before = s[t] - v;
-	__syncthreads();
-	return before;
-}
-static __global__ __launch_bounds__(GF_THREADS) void k_gfa_tile_sums(GfScan S)
-{
-	__shared__ gf_u64 s[GF_THREADS];
-	for (uint32_t t = blockIdx.x; t < S.n_tiles; t += gridDim.x) {
-		const gf_u64 i0 = (gf_u64)t * GF_TILE + (gf_u64)threadIdx.x * GF_ITEMS;
-		gf_u64 v = 0, total;
-		for (int k = 0; k < GF_ITEMS; ++k) if (i0 + k < S.n) v += S.val[i0 + k];
-		gf_block_excl(v, s, total);
-		if (threadIdx.x == 0) S.tile_sum[t] = total;
-	}
-}
-static __global__ __launch_bounds__(GF_THREADS) void k_gfa_tile_scan(GfScan S)
-{
-	__shared__ gf_u64 s[GF_THREADS];
-	gf_u64 run = 0;
-	for (uint32_t t0 = 0; t0 < S.n_tiles; t0 += GF_THREADS) {
-		const uint32_t t = t0 + threadIdx.x;
-		const gf_u64 v = t < S.n_tiles ? S.tile_sum[t] : 0ULL;
-		gf_u64 total;
-		const gf_u64 before = gf_block_excl(v, s, total);
-		if (t < S.n_tiles) S.tile_off[t] = run + before;
-		run += total;
-	}
-	if (threadIdx.x == 0) { S.tile_off[S.n_tiles] = run; S.off[S.n] = run; }
-}
-static __global__ __launch_bounds__(GF_THREADS) void k_gfa_offsets(GfScan S)
-{
-	__shared__ gf_u64 s[GF_THREADS];
-	for (uint32_t t = blockIdx.x; t < S.n_tiles; t += gridDim.x) {
-		const gf_u64 i0 = (gf_u64)t * GF_TILE + (gf_u64)threadIdx.x * GF_ITEMS;
-		gf_u64 c[GF_ITEMS], v = 0, total;
-		for (int k = 0; k < GF_ITEMS; ++k) { c[k] = i0 + k < S.n ? S.val[i0 + k] : 0ULL; v += c[k]; }
-		gf_u64 at = S.tile_off[t] + gf_block_excl(v, s, total);
-		for (int k = 0; k < GF_ITEMS && i0 + k < S.n; ++k) { S.off[i0 + k] = at; at += c[k]; }
-	}
-}
-
 // ---------------------------------------------------------------- 3. behind the scan of keep[]: the steps, the paths' shares, the link keys
 static __global__ __launch_bounds__(GF_THREADS) void k_gfa_steps(GfDev V)
 {
@@ -279,7 +218,7 @@ static __global__ __launch_bounds__(GF_THREADS) void k_gfa_row_off(GfDev V)
 static __global__ __launch_bounds__(GF_THREADS) void k_gfa_tile(GfDev V)
 {
 	__shared__ gf_u64 s_rng[2];
-	if (threadIdx.x < 2) s_rng[threadIdx.x] = gf_last_le(V.off, 0, V.n_items, threadIdx.x ? V.t1 - 1 : V.t0);
+	if (threadIdx.x < 2) s_rng[threadIdx.x] = ts_last_le(V.off, 0, V.n_items, threadIdx.x ? V.t1 - 1 : V.t0);
 	__syncthreads();
 	const gf_u64 lo = s_rng[0], hi = s_rng[1];
 	for (gf_u64 x = lo + (gf_u64)blockIdx.x * GF_THREADS + threadIdx.x; x <= hi; x += (gf_u64)gridDim.x * GF_THREADS) {

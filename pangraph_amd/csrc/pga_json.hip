@@ -16,55 +16,13 @@
 // The kernels and the host tables are pga_json_idx.h (no wave intrinsic: tests/emu/json_emu.cpp runs them on the host).
 // All arithmetic is integer; concurrent stores to one word store the same value or go through atomicMin.
 #include "pga_common.h"
+#include "pga_graph_host.h"
 #include "../../include/pga_align.h"
 #include "pga_json_idx.h"
-#include <chrono>
-#include <rocprim/rocprim.hpp>
 
 namespace pga {
 
-template <class T> static T *js_host_array(uint64_t n)
-{
-	T *p = (T*)calloc((size_t)(n ? n : 1), sizeof(T));
-	if (!p) js_fail("out of host memory");
-	return p;
-}
-static unsigned js_grid(uint64_t items) { return (unsigned)std::min<uint64_t>(std::max<uint64_t>((items + GF_THREADS - 1) / GF_THREADS, 1), 2048); }
-template <class T> static void js_up(DBuf<T> &d, const T *h, uint64_t n, hipStream_t st) { if (n) PGA_HIP(hipMemcpyAsync(d.p, h, n * sizeof(T), hipMemcpyHostToDevice, st)); }
-template <class T> static void js_fetch(T *dst, const T *src, uint64_t n, hipStream_t st) { if (n) PGA_HIP(hipMemcpyAsync(dst, src, n * sizeof(T), hipMemcpyDeviceToHost, st)); }
-template <class K> static void js_sort(const K *kin, K *kout, const uint32_t *vin, uint32_t *vout, uint64_t n, unsigned bits, hipStream_t st)
-{
-	if (!n) return;
-	size_t tb = 0;
-	PGA_HIP(rocprim::radix_sort_pairs(nullptr, tb, kin, kout, vin, vout, n, 0, bits, st));
-	DBuf<uint8_t> tmp(tb + 16);
-	PGA_HIP(rocprim::radix_sort_pairs(tmp.p, tb, kin, kout, vin, vout, n, 0, bits, st));
-}
-struct JsScanBufs {
-	DBuf<gf_u64> tile_sum, tile_off, off;
-	GfScan make(const gf_u64 *val, uint64_t n)
-	{
-		const uint32_t n_tiles = (uint32_t)((n + GF_TILE - 1) / GF_TILE);
-		tile_sum.alloc(n_tiles + 1); tile_off.alloc(n_tiles + 1); off.alloc(n + 1);
-		return GfScan{n, n_tiles, 0, val, tile_sum.p, tile_off.p, off.p};
-	}
-};
-static void js_scan(const GfScan &S, hipStream_t st)
-{
-	if (S.n_tiles) hipLaunchKernelGGL(k_gfa_tile_sums, dim3(std::min<uint32_t>(S.n_tiles, 2048u)), dim3(GF_THREADS), 0, st, S);
-	hipLaunchKernelGGL(k_gfa_tile_scan, dim3(1), dim3(GF_THREADS), 0, st, S);
-	if (S.n_tiles) hipLaunchKernelGGL(k_gfa_offsets, dim3(std::min<uint32_t>(S.n_tiles, 2048u)), dim3(GF_THREADS), 0, st, S);
-}
-// PGA_EXPORT_TILE_KB as pga_export.hip reads it: at every call
-static uint64_t js_tile_bytes()
-{
-	const char *e = getenv("PGA_EXPORT_TILE_KB");
-	if (!e || !*e) return 16384ULL * 1024;
-	char *end = nullptr;
-	const long long v = strtoll(e, &end, 10);
-	if (*end || v < 4 || v > (1LL << 31) || v % 4) js_fail(std::string("PGA_EXPORT_TILE_KB must be a whole number of KB, a multiple of 4 (got '") + e + "')");
-	return (uint64_t)v * 1024;
-}
+static unsigned js_grid(uint64_t items) { return grid_for(items, GF_THREADS, 2048); }
 // measurement only: PGA_JSON_INS_CHUNK overrides the letters of an insertion per item (the text does not depend on it)
 static uint32_t js_chunk()
 {
@@ -76,13 +34,8 @@ static uint32_t js_chunk()
 	return (uint32_t)v;
 }
 
-namespace {
-struct JsEvent { hipEvent_t e = nullptr; JsEvent() { PGA_HIP(hipEventCreate(&e)); } ~JsEvent() { (void)hipEventDestroy(e); } };
-struct JsPin { char *p = nullptr; ~JsPin() { pin_free(p); } };
-}
 static thread_local double g_js_ms[4] = {0, 0, 0, 0};
 void json_last_ms(double *ms) { for (int i = 0; i < 4; ++i) ms[i] = g_js_ms[i]; }
-static double js_now() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
 
 void export_json_host(int64_t n_blocks, const pga_topo_block_t *blocks, int64_t n_paths, const pga_topo_path_t *paths, int64_t n_nodes, const pga_topo_node_t *nodes,
                       const char *const *cons, const pga_rc_member_t *members, const pga_sub_t *subs, const pga_del_t *dels, const pga_ins_t *inss, const char *ins_seq,
@@ -91,10 +44,10 @@ void export_json_host(int64_t n_blocks, const pga_topo_block_t *blocks, int64_t 
 {
 	JsTables J;
 	js_validate(n_blocks, blocks, n_paths, paths, n_nodes, nodes, cons, members, subs, dels, inss, ins_seq, n_ins_seq, tot_len, names, name_len, descs, desc_len, flags, J);
-	const uint64_t tile_bytes = js_tile_bytes();
+	const uint64_t tile_bytes = export_tile_bytes(js_fail);
 	const uint32_t chunk = js_chunk();
 	const uint64_t nn = (uint64_t)n_nodes, np = (uint64_t)n_paths, nb = (uint64_t)n_blocks, ns = J.T.n_slots, na = J.ablk.size();
-	out->path_off = js_host_array<uint64_t>(np); out->block_off = js_host_array<uint64_t>(nb); out->node_order = js_host_array<uint32_t>(nn);
+	out->path_off = host_array<uint64_t>(np, "pga_export_json"); out->block_off = host_array<uint64_t>(nb, "pga_export_json"); out->node_order = host_array<uint32_t>(nn, "pga_export_json");
 	out->n_paths = n_paths; out->n_blocks = n_blocks; out->n_nodes = n_nodes;
 	if (nb == 0 && np == 0 && nn == 0) {
 		out->n_bytes = sizeof(JS_EMPTY) - 1; out->section_off[0] = 4; out->section_off[1] = 19; out->section_off[2] = 35;
@@ -104,7 +57,7 @@ void export_json_host(int64_t n_blocks, const pga_topo_block_t *blocks, int64_t 
 
 	// (declared before the streams: the streams are drained first when the scope is left, by a throw too)
 	DBuf<char> d_tile[2];
-	JsPin pin[2];
+	PinBlock pin[2];
 	DBuf<pga_topo_node_t> d_nodes(nn + 1); DBuf<pga_topo_path_t> d_paths(np + 1); DBuf<pga_topo_block_t> d_blocks(nb + 1); DBuf<JsPath> d_meta(np + 1);
 	DBuf<uint32_t> d_depth(nb + 1), d_first(nb + 2), d_pathof(nn + 1), d_cnts(ns + nb + 1), d_terr(TP_ERRS), d_ablk(na + 1);
 	DBuf<uint32_t> d_pos(nn + 1), d_order(nn + 1), d_bk(nn + 1), d_bsk(nn + 1), d_border(nn + 1);
@@ -113,16 +66,16 @@ void export_json_host(int64_t n_blocks, const pga_topo_block_t *blocks, int64_t 
 	DBuf<gf_u64> d_pathoff(np + 1), d_tailoff(np + 1), d_blockoff(nb + 1);
 	DBuf<pga_rc_member_t> d_members(ns + 1); DBuf<pga_sub_t> d_subs(J.n_subs + 1); DBuf<pga_del_t> d_dels(J.n_dels + 1); DBuf<pga_ins_t> d_inss(J.n_inss + 1);
 	DBuf<char> d_insseq(n_ins_seq + 1);
-	JsScanBufs b_s, b_d, b_i, b_c, b_m, b_items;
-	JsEvent ev_0, ev_1, ev_ka[2], ev_kb[2], ev_c[2];
+	TileScanBufs<gf_u64> b_s, b_d, b_i, b_c, b_m, b_items;
+	Event ev_0, ev_1, ev_ka[2], ev_kb[2], ev_c[2];
 	StreamLease s_kern, s_copy;
 	const hipStream_t st = s_kern.s, sc = s_copy.s;
 
 	// ---- the uploads, the checks of the graph as pga_plan_simplify makes them ----
 	PGA_HIP(hipEventRecord(ev_0.e, st));
-	js_up(d_nodes, nodes, nn, st); js_up(d_paths, paths, np, st); js_up(d_blocks, blocks, nb, st); js_up(d_meta, J.meta.data(), np, st);
-	js_up(d_depth, J.T.depth.data(), nb, st); js_up(d_first, J.T.slot_first.data(), nb + 1, st); js_up(d_ablk, J.ablk.data(), na, st);
-	js_up(d_members, members, ns, st); js_up(d_subs, subs, J.n_subs, st); js_up(d_dels, dels, J.n_dels, st); js_up(d_inss, inss, J.n_inss, st); js_up(d_insseq, ins_seq, n_ins_seq, st);
+	upload(d_nodes, nodes, nn, st); upload(d_paths, paths, np, st); upload(d_blocks, blocks, nb, st); upload(d_meta, J.meta.data(), np, st);
+	upload(d_depth, J.T.depth.data(), nb, st); upload(d_first, J.T.slot_first.data(), nb + 1, st); upload(d_ablk, J.ablk.data(), na, st);
+	upload(d_members, members, ns, st); upload(d_subs, subs, J.n_subs, st); upload(d_dels, dels, J.n_dels, st); upload(d_inss, inss, J.n_inss, st); upload(d_insseq, ins_seq, n_ins_seq, st);
 	d_cnts.zero(st);
 	PGA_HIP(hipMemsetAsync(d_terr.p, 0xff, TP_ERRS * sizeof(uint32_t), st));
 	PGA_HIP(hipMemsetAsync(d_jerr.p, 0xff, JS_ERRS * sizeof(gf_u64), st));
@@ -140,7 +93,7 @@ void export_json_host(int64_t n_blocks, const pga_topo_block_t *blocks, int64_t 
 	V.id_key = d_idk.p; V.pos = d_pos.p; V.id_skey = d_idsk.p; V.order = d_order.p; V.blk_key = d_bk.p; V.border = d_border.p; V.err = d_jerr.p;
 	V.cnt_s = d_cs.p; V.cnt_d = d_cd.p; V.cnt_i = d_ci.p; V.chunks = d_chunks.p; V.mitems = d_mitems.p; V.ablk = d_ablk.p; V.bstart = d_bstart.p;
 	V.path_off = d_pathoff.p; V.tail_off = d_tailoff.p; V.block_off = d_blockoff.p;
-	const GfScan s_s = b_s.make(d_cs.p, ns), s_d = b_d.make(d_cd.p, ns), s_i = b_i.make(d_ci.p, ns), s_c = b_c.make(d_chunks.p, J.n_inss), s_m = b_m.make(d_mitems.p, ns);
+	const GfScan s_s = b_s.make(ns, 1), s_d = b_d.make(ns, 1), s_i = b_i.make(ns, 1), s_c = b_c.make(J.n_inss, 1), s_m = b_m.make(ns, 1);
 	V.sub_off = s_s.off; V.del_off = s_d.off; V.ins_off = s_i.off; V.icoff = s_c.off; V.moff = s_m.off;
 	const unsigned g_pos = js_grid(nn + 1);
 	hipLaunchKernelGGL(k_topo_keys, dim3(g_pos), dim3(TP_THREADS), 0, st, K);
@@ -149,48 +102,48 @@ void export_json_host(int64_t n_blocks, const pga_topo_block_t *blocks, int64_t 
 	unsigned blk_bits = 1;
 	while (blk_bits < 32 && (nb >> blk_bits)) ++blk_bits;
 	hipLaunchKernelGGL(k_json_idkeys, dim3(g_pos), dim3(GF_THREADS), 0, st, V);
-	js_sort(d_idk.p, d_idsk.p, d_pos.p, d_order.p, nn, 64, st);
+	radix_sort_pairs(d_idk.p, d_idsk.p, d_pos.p, d_order.p, nn, 64, st);
 	hipLaunchKernelGGL(k_json_blkkeys, dim3(g_pos), dim3(GF_THREADS), 0, st, V);
-	js_sort(d_bk.p, d_bsk.p, d_order.p, d_border.p, nn, blk_bits, st);
+	radix_sort_pairs(d_bk.p, d_bsk.p, d_order.p, d_border.p, nn, blk_bits, st);
 	// ---- the edits ----
 	hipLaunchKernelGGL(k_json_counts, dim3(js_grid(ns)), dim3(GF_THREADS), 0, st, V);
-	js_scan(s_s, st); js_scan(s_d, st); js_scan(s_i, st);
+	tile_scan_launch(s_s, TsArray<gf_u64>{d_cs.p}, st); tile_scan_launch(s_d, TsArray<gf_u64>{d_cd.p}, st); tile_scan_launch(s_i, TsArray<gf_u64>{d_ci.p}, st);
 	hipLaunchKernelGGL(k_json_chunks, dim3(js_grid(J.n_inss)), dim3(GF_THREADS), 0, st, V);
-	js_scan(s_c, st);
+	tile_scan_launch(s_c, TsArray<gf_u64>{d_chunks.p}, st);
 	hipLaunchKernelGGL(k_json_check_subs, dim3(js_grid(J.n_subs)), dim3(GF_THREADS), 0, st, V);
 	hipLaunchKernelGGL(k_json_check_inss, dim3(js_grid(J.n_inss * 4)), dim3(GF_THREADS), 0, st, V);
 	PGA_HIP(hipGetLastError());
 	// ---- the first wait: nothing behind it runs on input that was not checked ----
 	uint32_t terr[TP_ERRS];
 	gf_u64 jerr[JS_ERRS], n_chunks = 0;
-	js_fetch(terr, (const uint32_t*)d_terr.p, TP_ERRS, st); js_fetch(jerr, (const gf_u64*)d_jerr.p, JS_ERRS, st); js_fetch(&n_chunks, (const gf_u64*)s_c.off + J.n_inss, 1, st);
-	js_fetch(out->node_order, (const uint32_t*)d_order.p, nn, st);
+	fetch(terr, (const uint32_t*)d_terr.p, TP_ERRS, st); fetch(jerr, (const gf_u64*)d_jerr.p, JS_ERRS, st); fetch(&n_chunks, (const gf_u64*)s_c.off + J.n_inss, 1, st);
+	fetch(out->node_order, (const uint32_t*)d_order.p, nn, st);
 	PGA_HIP(sync_stream(st));
 	js_report(terr, jerr);
 	if (ns != nn) js_fail("internal: the device accepted a graph whose slots and nodes differ in number");
 	js_bound(J, blocks, nn, n_chunks, chunk);
 	// ---- the hierarchy and the layout ----
 	hipLaunchKernelGGL(k_json_mitems, dim3(js_grid(ns)), dim3(GF_THREADS), 0, st, V);
-	js_scan(s_m, st);
+	tile_scan_launch(s_m, TsArray<gf_u64>{d_mitems.p}, st);
 	hipLaunchKernelGGL(k_json_bstart, dim3(js_grid(na + 1)), dim3(GF_THREADS), 0, st, V);
 	gf_u64 n_mitems = 0;
-	js_fetch(&n_mitems, (const gf_u64*)s_m.off + ns, 1, st);
+	fetch(&n_mitems, (const gf_u64*)s_m.off + ns, 1, st);
 	PGA_HIP(sync_stream(st));
 	V.n_pitems = nn + 2 * np; V.n_bitems = 2 * na + n_mitems; V.n_items = 4 + V.n_pitems + V.n_bitems + nn;
 	d_len.alloc(V.n_items + 1);
-	const GfScan s_items = b_items.make(d_len.p, V.n_items);
+	const GfScan s_items = b_items.make(V.n_items, 1);
 	V.len = d_len.p; V.off = s_items.off;
 	hipLaunchKernelGGL(k_json_lens, dim3(js_grid(V.n_items)), dim3(GF_THREADS), 0, st, V);
-	js_scan(s_items, st);
+	tile_scan_launch(s_items, TsArray<gf_u64>{d_len.p}, st);
 	hipLaunchKernelGGL(k_json_offs, dim3(js_grid(std::max(np, na))), dim3(GF_THREADS), 0, st, V);
 	PGA_HIP(hipGetLastError());
 	// ---- the wait behind the layout: the length of the file, where every key starts ----
 	std::vector<gf_u64> h_tailoff(np);
 	gf_u64 n_bytes = 0, sec[2] = {0, 0};
-	js_fetch(&n_bytes, (const gf_u64*)s_items.off + V.n_items, 1, st);
-	js_fetch(&sec[0], (const gf_u64*)s_items.off + 1 + V.n_pitems, 1, st); js_fetch(&sec[1], (const gf_u64*)s_items.off + 2 + V.n_pitems + V.n_bitems, 1, st);
-	js_fetch((gf_u64*)out->path_off, (const gf_u64*)d_pathoff.p, np, st); js_fetch((gf_u64*)out->block_off, (const gf_u64*)d_blockoff.p, nb, st);
-	js_fetch(h_tailoff.data(), (const gf_u64*)d_tailoff.p, np, st);
+	fetch(&n_bytes, (const gf_u64*)s_items.off + V.n_items, 1, st);
+	fetch(&sec[0], (const gf_u64*)s_items.off + 1 + V.n_pitems, 1, st); fetch(&sec[1], (const gf_u64*)s_items.off + 2 + V.n_pitems + V.n_bitems, 1, st);
+	fetch((gf_u64*)out->path_off, (const gf_u64*)d_pathoff.p, np, st); fetch((gf_u64*)out->block_off, (const gf_u64*)d_blockoff.p, nb, st);
+	fetch(h_tailoff.data(), (const gf_u64*)d_tailoff.p, np, st);
 	PGA_HIP(hipEventRecord(ev_1.e, st));
 	PGA_HIP(sync_stream(st));
 	if (n_bytes >= (1ULL << 63)) js_fail("a file of 2^63 bytes or more");
@@ -217,11 +170,11 @@ void export_json_host(int64_t n_blocks, const pga_topo_block_t *blocks, int64_t 
 	double ms_kern = 0, ms_fill = 0, ms_sink = 0;
 	auto deliver = [&](uint64_t t) {                                        // tile t lies in its pinned block: the host's letters, then the sink
 		gf_u64 a, z; span(t, a, z);
-		const double c0 = js_now();
+		const double c0 = now_ms();
 		js_host_fill(J, blocks, cons, pin[t & 1].p, a, z, pi, bi);
-		const double c1 = js_now();
+		const double c1 = now_ms();
 		const int rc = sink(ctx, pin[t & 1].p, (int64_t)(z - a));
-		ms_fill += c1 - c0; ms_sink += js_now() - c1;
+		ms_fill += c1 - c0; ms_sink += now_ms() - c1;
 		if (rc != 0) {
 			(void)hipStreamSynchronize(st); (void)hipStreamSynchronize(sc);     // drain what is in flight: no further sink call
 			js_fail("sink stopped the export");

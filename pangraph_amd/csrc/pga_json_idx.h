@@ -1,9 +1,9 @@
 // pga_json_idx.h -- the kernels and host tables of pga_json.hip (the pangraph JSON: serde_json::to_writer_pretty of Pangraph, written by
 // build_run.rs:78 and simplify_run.rs:20, on the flat graph of pga_plan_simplify and the block arrays of pga_reconsensus).
 // No wave intrinsic, plain stores and atomicMin only: all of this compiles under hipcc and, with dev/emu/hip_emu.h included first, under
-// g++ -std=c++17 -DPGA_EMU (tests/emu/json_emu.cpp runs it against a direct scalar construction).  The window, the decimal writer, the
-// lookup and the three scan kernels are pga_gfa_idx.h's, the path lookup and the graph checks pga_topo_idx.h's; the two radix sorts are
-// rocPRIM's (pga_json.hip) and are not in here.
+// g++ -std=c++17 -DPGA_EMU (tests/emu/json_emu.cpp runs it against a direct scalar construction).  The window and the decimal
+// writer are pga_gfa_idx.h's, the tile scan and the lookup in scanned offsets pga_tile_scan.h's, the path lookup and the graph checks
+// pga_topo_idx.h's; the two radix sorts are rocPRIM's (pga_json.hip) and are not in here.
 //
 // A POSITION is an index into nodes[]; a SLOT is (block, member) numbered slot_first[block] + member: members[], and with it the edit
 // lists, are in slot order.  The reference prints three BTreeMaps.  order[] holds the positions by ascending node_id (the "nodes" map);
@@ -112,12 +112,12 @@ __host__ __device__ __forceinline__ JsItem js_item(const JsDev &V, gf_u64 x)
 	if (x == 0) return JsItem{JS_K_BLOCKS, V.n_paths == 0, 0, 0};
 	x -= 1;
 	if (x < V.n_bitems) {
-		const gf_u64 k = gf_last_le(V.bstart, 0, V.n_alive, x);
+		const gf_u64 k = ts_last_le(V.bstart, 0, V.n_alive, x);
 		const uint32_t b = V.ablk[k];
 		const gf_u64 e0 = V.slot_first[b], e1 = V.slot_first[b + 1], j = x - V.bstart[k];
 		if (j == 0) return JsItem{JS_K_B_HEAD, k == 0, 0, b};
 		if (j == 1 + (V.moff[e1] - V.moff[e0])) return JsItem{JS_K_B_TAIL, e0 == e1, 0, b};
-		const gf_u64 y = V.moff[e0] + j - 1, e = gf_last_le(V.moff, e0, e1, y);
+		const gf_u64 y = V.moff[e0] + j - 1, e = ts_last_le(V.moff, e0, e1, y);
 		gf_u64 r = y - V.moff[e];
 		if (r == 0) return JsItem{JS_K_M_HEAD, e == e0, 0, e};
 		const pga_topo_node_t N = V.nodes[V.border[e]];
@@ -134,7 +134,7 @@ __host__ __device__ __forceinline__ JsItem js_item(const JsDev &V, gf_u64 x)
 		r -= 1;
 		const gf_u64 i0 = V.ins_off[s], i1 = i0 + M.n_inss;
 		if (r < V.icoff[i1] - V.icoff[i0]) {
-			const gf_u64 i = gf_last_le(V.icoff, i0, i1, V.icoff[i0] + r);
+			const gf_u64 i = ts_last_le(V.icoff, i0, i1, V.icoff[i0] + r);
 			return JsItem{JS_K_INS, i == i0, (uint32_t)(V.icoff[i0] + r - V.icoff[i]), i};
 		}
 		return JsItem{JS_K_M_TAIL, M.n_inss == 0, 0, 0};
@@ -240,7 +240,7 @@ static __global__ __launch_bounds__(GF_THREADS) void k_json_check_inss(JsDev V)
 {
 	const gf_u64 n = V.icoff[V.n_inss];
 	for (gf_u64 c = (gf_u64)blockIdx.x * GF_THREADS + threadIdx.x; c < n; c += (gf_u64)gridDim.x * GF_THREADS) {
-		const gf_u64 i = gf_last_le(V.icoff, 0, V.n_inss, c);
+		const gf_u64 i = ts_last_le(V.icoff, 0, V.n_inss, c);
 		const pga_ins_t S = V.inss[i];
 		if (S.seq_off > V.n_ins_seq || S.len > V.n_ins_seq - S.seq_off) { atomicMin(&V.err[JS_E_INS_RANGE], i); continue; }
 		const gf_u64 a = (c - V.icoff[i]) * V.chunk, z = S.len - a < V.chunk ? S.len : a + V.chunk;
@@ -291,7 +291,7 @@ static __global__ __launch_bounds__(GF_THREADS) void k_json_offs(JsDev V)
 static __global__ __launch_bounds__(GF_THREADS) void k_json_tile(JsDev V)
 {
 	__shared__ gf_u64 s_rng[2];
-	if (threadIdx.x < 2) s_rng[threadIdx.x] = gf_last_le(V.off, 0, V.n_items, threadIdx.x ? V.t1 - 1 : V.t0);
+	if (threadIdx.x < 2) s_rng[threadIdx.x] = ts_last_le(V.off, 0, V.n_items, threadIdx.x ? V.t1 - 1 : V.t0);
 	__syncthreads();
 	const gf_u64 lo = s_rng[0], hi = s_rng[1];
 	for (gf_u64 x = lo + (gf_u64)blockIdx.x * GF_THREADS + threadIdx.x; x <= hi; x += (gf_u64)gridDim.x * GF_THREADS) {

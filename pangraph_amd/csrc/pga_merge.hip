@@ -16,17 +16,13 @@
 // The list kernels and the tables are pga_merge_idx.h (no wave intrinsic: tests/emu/merge_emu.cpp runs them on the host).
 // All arithmetic is integer; atomics feed only sums, counts, minima and flags, so the result does not depend on the launch geometry.
 #include "pga_common.h"
+#include "pga_graph_host.h"
+#include "pga_wave.h"
 #include "../../include/pga_align.h"
 #include "pga_merge_idx.h"
 
 namespace pga {
 
-__device__ __forceinline__ mg_u64 mg_wave_incl(mg_u64 v, uint32_t lane)
-{
-#pragma unroll
-	for (int d = 1; d < 64; d <<= 1) { const mg_u64 o = __shfl_up(v, d); if ((int)lane >= d) v += o; }
-	return v;
-}
 // ONE wave: ins_off[o] = the output insertions of the members before o; ins_off[n] = their total
 __global__ __launch_bounds__(64) void k_merge_scan(const uint32_t *n_ins, uint64_t n, mg_u64 *ins_off)
 {
@@ -34,20 +30,14 @@ __global__ __launch_bounds__(64) void k_merge_scan(const uint32_t *n_ins, uint64
 	mg_u64 run = 0;
 	for (uint64_t c0 = 0; c0 < n; c0 += 64) {
 		const uint64_t o = c0 + lane;
-		const mg_u64 v = o < n ? (mg_u64)n_ins[o] : 0ULL, in = mg_wave_incl(v, lane);
+		const mg_u64 v = o < n ? (mg_u64)n_ins[o] : 0ULL, in = wave_incl_u64(v, lane);
 		if (o < n) ins_off[o] = run + in - v;
 		run += __shfl(in, 63);
 	}
 	if (lane == 0) ins_off[n] = run;
 }
 
-template <class T> static T *mg_host_array(uint64_t n)
-{
-	T *p = (T*)calloc((size_t)(n ? n : 1), sizeof(T));
-	if (!p) throw std::runtime_error("pga_merge_blocks: out of host memory");
-	return p;
-}
-static unsigned mg_grid(uint64_t items, uint64_t per_block) { return (unsigned)std::min<uint64_t>(std::max<uint64_t>((items + per_block - 1) / per_block, 1), 1u << 16); }
+static unsigned mg_grid(uint64_t items, uint64_t per_block) { return grid_for(items, per_block, 1u << 16); }
 
 void merge_blocks_host(int64_t n_blocks, const pga_rc_block_t *blocks, const pga_rc_member_t *members, const pga_sub_t *subs, const pga_del_t *dels, const pga_ins_t *inss,
                        const char *ins_seq, int64_t n_edges, const pga_merge_edge_t *edges, const uint32_t *partner, pga_merge_out_t *out)
@@ -59,19 +49,19 @@ void merge_blocks_host(int64_t n_blocks, const pga_rc_block_t *blocks, const pga
 	MgTables T;
 	mg_build_tables(G, n_edges, edges, partner, T);
 	const uint64_t n_mem = T.mem.size(), n_jobs = T.jobs.size();
-	out->edges = mg_host_array<pga_merge_res_t>((uint64_t)n_edges);
-	out->blocks = mg_host_array<pga_rc_block_t>((uint64_t)n_edges);
-	out->members = mg_host_array<pga_rc_member_t>(n_mem);
-	out->subs = mg_host_array<pga_sub_t>(T.n_sub); out->dels = mg_host_array<pga_del_t>(T.n_del);
+	out->edges = host_array<pga_merge_res_t>((uint64_t)n_edges, "pga_merge_blocks");
+	out->blocks = host_array<pga_rc_block_t>((uint64_t)n_edges, "pga_merge_blocks");
+	out->members = host_array<pga_rc_member_t>(n_mem, "pga_merge_blocks");
+	out->subs = host_array<pga_sub_t>(T.n_sub, "pga_merge_blocks"); out->dels = host_array<pga_del_t>(T.n_del, "pga_merge_blocks");
 	const uint64_t cons_bytes = T.cons_units * ROW_LETTERS, ins_bytes = (T.units - T.cons_units) * ROW_LETTERS;
-	out->cons = mg_host_array<char>(cons_bytes + 1); out->ins_seq = mg_host_array<char>(ins_bytes + 1);
+	out->cons = host_array<char>(cons_bytes + 1, "pga_merge_blocks"); out->ins_seq = host_array<char>(ins_bytes + 1, "pga_merge_blocks");
 	for (int64_t e = 0; e < n_edges; ++e) {
 		out->edges[e].member_off = T.member_off[e];
 		out->blocks[e].consensus = out->cons + T.cons_off[e];
 		out->blocks[e].cons_len = blocks[edges[e].left].cons_len + blocks[edges[e].right].cons_len;
 		out->blocks[e].n_members = blocks[edges[e].left].n_members;
 	}
-	if (n_edges == 0 || (n_mem == 0 && n_jobs == 0)) { out->inss = mg_host_array<pga_ins_t>(0); return; }   // (only empty blocks: nothing to build)
+	if (n_edges == 0 || (n_mem == 0 && n_jobs == 0)) { out->inss = host_array<pga_ins_t>(0, "pga_merge_blocks"); return; }   // (only empty blocks: nothing to build)
 	// ---- the device ----
 	StreamLease stream;
 	hipStream_t st = stream.s;
@@ -113,7 +103,7 @@ void merge_blocks_host(int64_t n_blocks, const pga_rc_block_t *blocks, const pga
 		hipLaunchKernelGGL(k_merge_write, dim3(mg_grid(n_mem, MG_WAVES)), dim3(MG_THREADS), 0, st, V, d_osubs.p, d_odels.p, d_oinss.p, d_runs.p);
 		PGA_HIP(hipGetLastError());
 	}
-	out->inss = mg_host_array<pga_ins_t>(n_ins_out);
+	out->inss = host_array<pga_ins_t>(n_ins_out, "pga_merge_blocks");
 	// ---- the letters: consensus rows, then the rows of inserted letters, one unit space ----
 	const uint64_t il = T.ins_lo < T.ins_hi ? T.ins_lo : 0, ih = T.ins_lo < T.ins_hi ? T.ins_hi : 0;
 	DBuf<char> d_cons(T.cons.size() + 16), d_iseq(ih - il + 16), d_out(T.units * ROW_LETTERS + 16);

@@ -1,7 +1,7 @@
 // pga_merge_idx.h -- the index arithmetic of pga_merge.hip (merge_blocks.rs:92-148 concatenate_alignments over PangraphBlock::reverse_complement,
 // pangraph_block.rs:63-75, and Edit::{reverse_complement, shift, concat}, edits.rs:257-304): the host tables and the list kernels.  None of
 // them uses a wave intrinsic, so all of this compiles under hipcc and, with dev/emu/hip_emu.h included first, under g++ -std=c++17 -DPGA_EMU
-// (tests/emu/merge_emu.cpp runs it against a direct scalar construction).  The one-wave scan of pga_merge.hip is not in here.
+// (tests/emu/merge_emu.cpp runs it against a direct scalar construction).  The one-wave scan of pga_merge.hip (wave_incl_u64 of pga_wave.h) is not in here.
 //
 // An OUTPUT MEMBER is (edge, k): the k-th member of the edge's left block joined with member partner[k] of its right block.  Each of its
 // two SIDES is one input member read through its block's orientation:

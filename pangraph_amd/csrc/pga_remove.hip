@@ -5,7 +5,7 @@
 //   host               validation (all of it before anything is launched), the totals of the three lists, the path table after (O(paths))
 //   k_topo_keys / _check   pga_topo_idx.h: the path of every position, every (block, member) slot named exactly once
 //   k_remove_mark      one thread per position: the members of kept paths
-//   k_remove_tile_sums / _tile_scan / _offsets <members>   seven exclusive sums over the members, side by side: the kept flag, where the
+//   k_ts_sums / _scan / _offsets (pga_tile_scan.h), members   seven exclusive sums over the members, side by side: the kept flag, where the
 //                      three lists of a member start in the input, where they start in the output
 //   host               the first wait: the checks, the totals
 //   k_remove_blocks / _members / _nodes   kept counts per block, member_map, the slot renumbering, the nodes at their places
@@ -16,50 +16,18 @@
 // The kernels and the host tables are pga_remove_idx.h (no wave intrinsic: tests/emu/remove_emu.cpp runs them on the host).
 // All arithmetic is integer; atomics feed only minima, so the result does not depend on the launch geometry.
 #include "pga_common.h"
+#include "pga_graph_host.h"
 #include "../../include/pga_align.h"
 #include "pga_remove_idx.h"
 
 namespace pga {
 
-template <class T> static T *rm_host_array(uint64_t n)
-{
-	T *p = (T*)calloc((size_t)(n ? n : 1), sizeof(T));
-	if (!p) throw std::runtime_error("pga_remove_paths: out of host memory");
-	return p;
-}
-static unsigned rm_grid(uint64_t items) { return (unsigned)std::min<uint64_t>(std::max<uint64_t>((items + RM_THREADS - 1) / RM_THREADS, 1), 2048); }
-static unsigned rm_tile_grid(uint64_t items) { return (unsigned)std::min<uint64_t>(std::max<uint64_t>((items + RM_TILE - 1) / RM_TILE, 1), 1u << 16); }
-template <class T> static void rm_up(DBuf<T> &d, const T *h, uint64_t n, hipStream_t st) { if (n) PGA_HIP(hipMemcpyAsync(d.p, h, n * sizeof(T), hipMemcpyHostToDevice, st)); }
-template <class T> static void rm_fetch(T *dst, const T *src, uint64_t n, hipStream_t st) { if (n) PGA_HIP(hipMemcpyAsync(dst, src, n * sizeof(T), hipMemcpyDeviceToHost, st)); }
-
-// the scan's buffers: every one an entry longer than its count, none is empty
-struct RmScanBufs {
-	DBuf<rm_u64> tile_sum, tile_off, off;
-	RmScan make(uint64_t n, uint32_t n_q)
-	{
-		const uint32_t n_tiles = (uint32_t)((n + RM_TILE - 1) / RM_TILE);
-		tile_sum.alloc((uint64_t)n_q * n_tiles + 1); tile_off.alloc((uint64_t)n_q * (n_tiles + 1)); off.alloc((uint64_t)n_q * (n + 1));
-		return RmScan{n, n_tiles, n_q, tile_sum.p, tile_off.p, off.p};
-	}
-};
-template <int K> static void rm_scan(const RmDev &V, hipStream_t st)
-{
-	const uint32_t n_tiles = V.scan[K].n_tiles;
-	if (n_tiles) hipLaunchKernelGGL(k_remove_tile_sums<K>, dim3(std::min<uint32_t>(n_tiles, 2048u)), dim3(RM_THREADS), 0, st, V);
-	hipLaunchKernelGGL(k_remove_tile_scan<K>, dim3(1), dim3(RM_THREADS), 0, st, V);
-	if (n_tiles) hipLaunchKernelGGL(k_remove_offsets<K>, dim3(std::min<uint32_t>(n_tiles, 2048u)), dim3(RM_THREADS), 0, st, V);
-}
+static unsigned rm_grid(uint64_t items) { return grid_for(items, RM_THREADS, 2048); }
+static unsigned rm_tile_grid(uint64_t items) { return grid_for(items, RM_TILE, 1u << 16); }
 
 // the stream's clock at four places of the last call of this thread: upload, kernels (their waits included), download, in ms
 static thread_local double g_rm_ms[3] = {0, 0, 0};
 void remove_last_ms(double *ms) { for (int i = 0; i < 3; ++i) ms[i] = g_rm_ms[i]; }
-struct RmClock {
-	hipEvent_t e[4]; hipStream_t st;
-	explicit RmClock(hipStream_t s) : st(s) { for (hipEvent_t &x : e) PGA_HIP(hipEventCreate(&x)); }
-	void at(int i) { PGA_HIP(hipEventRecord(e[i], st)); }
-	void read() { for (int i = 0; i < 3; ++i) { float ms = 0; PGA_HIP(hipEventElapsedTime(&ms, e[i], e[i + 1])); g_rm_ms[i] = ms; } }
-	~RmClock() { for (hipEvent_t &x : e) (void)hipEventDestroy(x); }
-};
 
 void remove_paths_host(int64_t n_blocks, const pga_topo_block_t *blocks, int64_t n_paths, const pga_topo_path_t *paths, int64_t n_nodes, const pga_topo_node_t *nodes,
                        const pga_rc_block_t *rc_blocks, const pga_rc_member_t *members, const pga_sub_t *subs, const pga_del_t *dels, const pga_ins_t *inss,
@@ -70,8 +38,8 @@ void remove_paths_host(int64_t n_blocks, const pga_topo_block_t *blocks, int64_t
 	const uint64_t nn = (uint64_t)n_nodes, np = (uint64_t)n_paths, nb = (uint64_t)n_blocks, nm = R.n_members, np_out = R.o_paths.size(), nn_out = R.n_out_nodes;
 	const bool letters = (flags & PGA_REMOVE_COMPACT_LETTERS) != 0;
 	out->n_blocks = n_blocks;
-	out->blocks = rm_host_array<pga_topo_block_t>(nb); out->rc_blocks = rm_host_array<pga_rc_block_t>(nb);
-	out->path_map = rm_host_array<int32_t>(np); out->member_map = rm_host_array<int64_t>(nm);
+	out->blocks = host_array<pga_topo_block_t>(nb, "pga_remove_paths"); out->rc_blocks = host_array<pga_rc_block_t>(nb, "pga_remove_paths");
+	out->path_map = host_array<int32_t>(np, "pga_remove_paths"); out->member_map = host_array<int64_t>(nm, "pga_remove_paths");
 	if (n_paths == 0) {                                                      // no path, so no member (rm_validate): nothing to launch
 		for (uint64_t b = 0; b < nb; ++b) {
 			const bool alive = blocks[b].alive != 0;
@@ -79,17 +47,17 @@ void remove_paths_host(int64_t n_blocks, const pga_topo_block_t *blocks, int64_t
 			out->rc_blocks[b] = pga_rc_block_t{rc_blocks[b].consensus, rc_blocks[b].cons_len, 0u};
 			out->n_dead_blocks += alive ? 0 : 1;
 		}
-		out->paths = rm_host_array<pga_topo_path_t>(0); out->nodes = rm_host_array<pga_topo_node_t>(0); out->members = rm_host_array<pga_rc_member_t>(0);
-		out->subs = rm_host_array<pga_sub_t>(0); out->dels = rm_host_array<pga_del_t>(0); out->inss = rm_host_array<pga_ins_t>(0);
-		if (letters) out->ins_seq = rm_host_array<char>(0);
+		out->paths = host_array<pga_topo_path_t>(0, "pga_remove_paths"); out->nodes = host_array<pga_topo_node_t>(0, "pga_remove_paths"); out->members = host_array<pga_rc_member_t>(0, "pga_remove_paths");
+		out->subs = host_array<pga_sub_t>(0, "pga_remove_paths"); out->dels = host_array<pga_del_t>(0, "pga_remove_paths"); out->inss = host_array<pga_ins_t>(0, "pga_remove_paths");
+		if (letters) out->ins_seq = host_array<char>(0, "pga_remove_paths");
 		return;
 	}
 	out->n_paths = (int64_t)np_out; out->n_nodes = (int64_t)nn_out;
-	out->paths = rm_host_array<pga_topo_path_t>(np_out); out->nodes = rm_host_array<pga_topo_node_t>(nn_out);
+	out->paths = host_array<pga_topo_path_t>(np_out, "pga_remove_paths"); out->nodes = host_array<pga_topo_node_t>(nn_out, "pga_remove_paths");
 	std::copy(R.o_paths.begin(), R.o_paths.end(), out->paths); std::copy(R.path_map.begin(), R.path_map.end(), out->path_map);
 	StreamLease stream;
 	hipStream_t st = stream.s;
-	RmClock clock(st);
+	StageClock clock(st);
 	clock.at(0);
 	// ---- the uploads (every buffer one entry longer than its count: none is empty) ----
 	const uint64_t n_letters_in = letters && ins_seq ? ins_seq_len : 0;
@@ -97,10 +65,10 @@ void remove_paths_host(int64_t n_blocks, const pga_topo_block_t *blocks, int64_t
 	DBuf<uint32_t> d_depth(nb + 1), d_first(nb + 1), d_mkeep(nm + 1); DBuf<uint8_t> d_keep(np + 1); DBuf<rm_u64> d_newoff(np + 1);
 	DBuf<pga_rc_member_t> d_members(nm + 1); DBuf<pga_sub_t> d_subs(R.n_subs + 1); DBuf<pga_del_t> d_dels(R.n_dels + 1); DBuf<pga_ins_t> d_inss(R.n_inss + 1);
 	DBuf<char> d_seq(n_letters_in + 1);
-	rm_up(d_nodes, nodes, nn, st); rm_up(d_paths, paths, np, st); rm_up(d_blocks, blocks, nb, st);
-	rm_up(d_depth, R.T.depth.data(), nb, st); rm_up(d_first, R.T.slot_first.data(), nb + 1, st); rm_up(d_keep, keep, np, st);
-	rm_up(d_newoff, (const rm_u64*)R.path_new_off.data(), np, st); rm_up(d_members, members, nm, st);
-	rm_up(d_subs, subs, R.n_subs, st); rm_up(d_dels, dels, R.n_dels, st); rm_up(d_inss, inss, R.n_inss, st); rm_up(d_seq, ins_seq, n_letters_in, st);
+	upload(d_nodes, nodes, nn, st); upload(d_paths, paths, np, st); upload(d_blocks, blocks, nb, st);
+	upload(d_depth, R.T.depth.data(), nb, st); upload(d_first, R.T.slot_first.data(), nb + 1, st); upload(d_keep, keep, np, st);
+	upload(d_newoff, (const rm_u64*)R.path_new_off.data(), np, st); upload(d_members, members, nm, st);
+	upload(d_subs, subs, R.n_subs, st); upload(d_dels, dels, R.n_dels, st); upload(d_inss, inss, R.n_inss, st); upload(d_seq, ins_seq, n_letters_in, st);
 	clock.at(1);
 	// ---- the checks of the graph, as pga_plan_simplify makes them; the kept members; the member scan ----
 	DBuf<uint32_t> d_pathof(nn + 1), d_cnts(nm + nb + 1), d_terr(TP_ERRS);
@@ -113,7 +81,7 @@ void remove_paths_host(int64_t n_blocks, const pga_topo_block_t *blocks, int64_t
 	T.n_nodes = nn; T.n_paths = np; T.n_blocks = nb; T.n_slots = nm;
 	T.nodes = d_nodes.p; T.paths = d_paths.p; T.depth = d_depth.p; T.slot_first = d_first.p; T.path_of = d_pathof.p; T.key = d_key.p;
 	T.slot_cnt = d_cnts.p; T.blk_cnt = d_cnts.p + nm; T.err = d_terr.p;
-	RmScanBufs b_mem, b_let;
+	TileScanBufs<rm_u64> b_mem, b_let;
 	RmDev V;
 	memset(&V, 0, sizeof(V));
 	V.n_nodes = nn; V.n_paths = np; V.n_blocks = nb; V.n_members = nm; V.ins_seq_len = ins_seq_len; V.flags = flags;
@@ -124,13 +92,13 @@ void remove_paths_host(int64_t n_blocks, const pga_topo_block_t *blocks, int64_t
 	hipLaunchKernelGGL(k_topo_keys, dim3(rm_grid(nn)), dim3(TP_THREADS), 0, st, T);
 	hipLaunchKernelGGL(k_topo_check, dim3(rm_grid(std::max(nm, nb))), dim3(TP_THREADS), 0, st, T);
 	hipLaunchKernelGGL(k_remove_mark, dim3(rm_grid(nn)), dim3(RM_THREADS), 0, st, V);
-	rm_scan<RM_SCAN_MEMBERS>(V, st);
+	tile_scan_launch(V.scan[RM_SCAN_MEMBERS], RmMemberValue{V}, st);
 	PGA_HIP(hipGetLastError());
 	// ---- the first wait: nothing behind it runs on input that was not checked ----
 	uint32_t terr[TP_ERRS];
 	rm_u64 tot[RM_QS];
-	rm_fetch(terr, (const uint32_t*)d_terr.p, TP_ERRS, st);
-	for (int q = 0; q < RM_QS; ++q) rm_fetch(&tot[q], rm_off(V.scan[RM_SCAN_MEMBERS], q) + nm, 1, st);
+	fetch(terr, (const uint32_t*)d_terr.p, TP_ERRS, st);
+	for (int q = 0; q < RM_QS; ++q) fetch(&tot[q], ts_off(V.scan[RM_SCAN_MEMBERS], q) + nm, 1, st);
 	PGA_HIP(sync_stream(st));
 	rm_report(terr);
 	if (tot[RM_Q_IN_SUB] != R.n_subs || tot[RM_Q_IN_DEL] != R.n_dels || tot[RM_Q_IN_INS] != R.n_inss || tot[RM_Q_KEPT] > nm || tot[RM_Q_OUT_SUB] > R.n_subs ||
@@ -152,10 +120,10 @@ void remove_paths_host(int64_t n_blocks, const pga_topo_block_t *blocks, int64_t
 	DBuf<char> d_oseq;
 	if (letters) {
 		V.scan[RM_SCAN_LETTERS] = b_let.make(ni_out, 1);
-		rm_scan<RM_SCAN_LETTERS>(V, st);
+		tile_scan_launch(V.scan[RM_SCAN_LETTERS], RmLetterValue{V}, st);
 		PGA_HIP(hipGetLastError());
 		rm_u64 err[RM_ERRS], n_let = 0;
-		rm_fetch(err, (const rm_u64*)d_err.p, RM_ERRS, st); rm_fetch(&n_let, rm_off(V.scan[RM_SCAN_LETTERS], 0) + ni_out, 1, st);
+		fetch(err, (const rm_u64*)d_err.p, RM_ERRS, st); fetch(&n_let, ts_off(V.scan[RM_SCAN_LETTERS], 0) + ni_out, 1, st);
 		PGA_HIP(sync_stream(st));
 		rm_report_letters(err);                                                  // (before a letter is read)
 		nl_out = n_let;
@@ -167,17 +135,17 @@ void remove_paths_host(int64_t n_blocks, const pga_topo_block_t *blocks, int64_t
 	}
 	clock.at(2);
 	// ---- the output ----
-	out->members = rm_host_array<pga_rc_member_t>(nm_out); out->subs = rm_host_array<pga_sub_t>(ns_out); out->dels = rm_host_array<pga_del_t>(nd_out);
-	out->inss = rm_host_array<pga_ins_t>(ni_out);
-	if (letters) out->ins_seq = rm_host_array<char>(nl_out + 1);
-	rm_fetch(out->blocks, (const pga_topo_block_t*)d_oblocks.p, nb, st); rm_fetch(out->nodes, (const pga_topo_node_t*)d_onodes.p, nn_out, st);
-	rm_fetch(out->members, (const pga_rc_member_t*)d_omembers.p, nm_out, st); rm_fetch(out->subs, (const pga_sub_t*)d_osubs.p, ns_out, st);
-	rm_fetch(out->dels, (const pga_del_t*)d_odels.p, nd_out, st); rm_fetch(out->inss, (const pga_ins_t*)d_oinss.p, ni_out, st);
-	rm_fetch((long long*)out->member_map, (const long long*)d_map.p, nm, st);
-	if (letters) rm_fetch(out->ins_seq, (const char*)d_oseq.p, nl_out, st);
+	out->members = host_array<pga_rc_member_t>(nm_out, "pga_remove_paths"); out->subs = host_array<pga_sub_t>(ns_out, "pga_remove_paths"); out->dels = host_array<pga_del_t>(nd_out, "pga_remove_paths");
+	out->inss = host_array<pga_ins_t>(ni_out, "pga_remove_paths");
+	if (letters) out->ins_seq = host_array<char>(nl_out + 1, "pga_remove_paths");
+	fetch(out->blocks, (const pga_topo_block_t*)d_oblocks.p, nb, st); fetch(out->nodes, (const pga_topo_node_t*)d_onodes.p, nn_out, st);
+	fetch(out->members, (const pga_rc_member_t*)d_omembers.p, nm_out, st); fetch(out->subs, (const pga_sub_t*)d_osubs.p, ns_out, st);
+	fetch(out->dels, (const pga_del_t*)d_odels.p, nd_out, st); fetch(out->inss, (const pga_ins_t*)d_oinss.p, ni_out, st);
+	fetch((long long*)out->member_map, (const long long*)d_map.p, nm, st);
+	if (letters) fetch(out->ins_seq, (const char*)d_oseq.p, nl_out, st);
 	clock.at(3);
 	PGA_HIP(sync_stream(st));
-	clock.read();
+	clock.read(g_rm_ms);
 	for (uint64_t b = 0; b < nb; ++b) {
 		out->rc_blocks[b] = pga_rc_block_t{rc_blocks[b].consensus, rc_blocks[b].cons_len, out->blocks[b].depth};
 		out->n_dead_blocks += out->blocks[b].alive ? 0 : 1;

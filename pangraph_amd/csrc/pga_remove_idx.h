@@ -2,8 +2,8 @@
 // pangraph/pangraph.rs:110-132, for every path that is not kept, on the flat graph of pga_plan_simplify and the block arrays of pga_merge_blocks).
 // No wave intrinsic, atomicAdd / atomicMin only: all of this compiles under hipcc and, with dev/emu/hip_emu.h included first, under
 // g++ -std=c++17 -DPGA_EMU (tests/emu/remove_emu.cpp runs it against a direct scalar construction).
-// The path lookup and the graph checks are pga_topo_idx.h's; the scans are the tile scan of that header over 64-bit values, several
-// quantities side by side.
+// The path lookup and the graph checks are pga_topo_idx.h's; the scans are the tile scan of pga_tile_scan.h over 64-bit values, several
+// quantities side by side, with the value functors below.
 //
 // A MEMBER is a global member, first_member[block] + member: the SLOT of pga_topo_idx.h under another name (a dead block has no member, so
 // slot_first[] is first_member[]).  It is KEPT when the path of the node that names it is.  A path is kept or removed as a whole, so a kept
@@ -20,15 +20,14 @@
 namespace pga {
 
 typedef unsigned long long rm_u64;
-constexpr int RM_THREADS = TP_THREADS, RM_ITEMS = TP_ITEMS, RM_TILE = TP_TILE;
+constexpr int RM_THREADS = TS_THREADS, RM_TILE = TS_TILE;
 enum { RM_Q_KEPT = 0, RM_Q_IN_SUB = 1, RM_Q_IN_DEL = 2, RM_Q_IN_INS = 3, RM_Q_OUT_SUB = 4, RM_Q_OUT_DEL = 5, RM_Q_OUT_INS = 6, RM_QS = 7 };
 enum { RM_SCAN_MEMBERS = 0, RM_SCAN_LETTERS = 1, RM_SCANS = 2 };
 enum { RM_LIST_SUB = 0, RM_LIST_DEL = 1, RM_LIST_INS = 2 };
 enum { RM_E_INS_NULL = 0, RM_E_INS_RANGE = 1, RM_ERRS = 2 };              // err[]: the lowest offending insertion of the output, all-ones = none
 constexpr rm_u64 RM_NONE = ~0ULL;
 
-// one scan: n items, n_q quantities; tile_sum: n_q x n_tiles; tile_off: n_q x (n_tiles + 1); off: n_q x (n + 1), off[q][n] the total
-struct RmScan { rm_u64 n; uint32_t n_tiles, n_q; rm_u64 *tile_sum, *tile_off, *off; };
+typedef TileScan<rm_u64> RmScan;                                           // pga_tile_scan.h: n_q quantities side by side
 struct RmDev {
 	uint64_t n_nodes, n_paths, n_blocks, n_members, ins_seq_len;
 	uint32_t flags, pad;
@@ -45,25 +44,20 @@ struct RmDev {
 	rm_u64 *err;                                           // RM_ERRS words
 };
 
-__host__ __device__ inline const rm_u64 *rm_off(const RmScan &S, int q) { return S.off + (rm_u64)q * (S.n + 1); }
-// the last index x in [lo, hi) with off[x] <= j, given off[lo] <= j < off[hi]: the item that holds element j (empty items share their
-// offset with the item behind them)
-__host__ __device__ inline rm_u64 rm_last_le(const rm_u64 *off, rm_u64 lo, rm_u64 hi, rm_u64 j)
-{
-	while (hi - lo > 1) { const rm_u64 mid = (lo + hi) >> 1; if (off[mid] <= j) lo = mid; else hi = mid; }
-	return lo;
-}
-template <int K> __host__ __device__ inline rm_u64 rm_value(const RmDev &V, int q, rm_u64 i);
-template <> __host__ __device__ inline rm_u64 rm_value<RM_SCAN_MEMBERS>(const RmDev &V, int q, rm_u64 i)
-{
-	const rm_u64 kept = V.mkeep[i] ? 1ULL : 0ULL;
-	if (q == RM_Q_KEPT) return kept;
-	const pga_rc_member_t M = V.members[i];
-	const int list = (q - 1) % 3;
-	const rm_u64 n = list == RM_LIST_SUB ? M.n_subs : list == RM_LIST_DEL ? M.n_dels : M.n_inss;
-	return q >= RM_Q_OUT_SUB ? n * kept : n;
-}
-template <> __host__ __device__ inline rm_u64 rm_value<RM_SCAN_LETTERS>(const RmDev &V, int, rm_u64 i) { return V.o_inss[i].len; }
+// what a member is worth in the member scan, an output insertion in the letter scan
+struct RmMemberValue {
+	RmDev V;
+	__host__ __device__ rm_u64 operator()(int q, uint64_t i) const
+	{
+		const rm_u64 kept = V.mkeep[i] ? 1ULL : 0ULL;
+		if (q == RM_Q_KEPT) return kept;
+		const pga_rc_member_t M = V.members[i];
+		const int list = (q - 1) % 3;
+		const rm_u64 n = list == RM_LIST_SUB ? M.n_subs : list == RM_LIST_DEL ? M.n_dels : M.n_inss;
+		return q >= RM_Q_OUT_SUB ? n * kept : n;
+	}
+};
+struct RmLetterValue { RmDev V; __host__ __device__ rm_u64 operator()(int, uint64_t i) const { return V.o_inss[i].len; } };
 
 // ---------------------------------------------------------------- 1. which members stay, one thread per position
 static __global__ __launch_bounds__(RM_THREADS) void k_remove_mark(RmDev V)
@@ -72,76 +66,13 @@ static __global__ __launch_bounds__(RM_THREADS) void k_remove_mark(RmDev V)
 		if (V.keep[V.path_of[i]]) V.mkeep[V.slot_first[V.nodes[i].block] + V.nodes[i].member] = 1u;   // (block and member were checked on the host)
 }
 
-// ---------------------------------------------------------------- 2. the scans: tile sums, ONE workgroup over them, the offsets
-// exclusive sums of one value per thread over the workgroup, through LDS; total: the workgroup's sum (tp_block_excl over 64 bits)
-__device__ inline rm_u64 rm_block_excl(rm_u64 v, rm_u64 *s, rm_u64 &total)
-{
-	const uint32_t t = threadIdx.x;
-	s[t] = v;
-	__syncthreads();
-	for (uint32_t d = 1; d < (uint32_t)RM_THREADS; d <<= 1) {
-		const rm_u64 x = t >= d ? s[t - d] : 0ULL;
-		__syncthreads();
-		s[t] += x;
-		__syncthreads();
-	}
-	total = s[RM_THREADS - 1];
-	const rm_u64 before = s[t] - v;
-	__syncthreads();
-	return before;
-}
-template <int K> static __global__ __launch_bounds__(RM_THREADS) void k_remove_tile_sums(RmDev V)
-{
-	__shared__ rm_u64 s[RM_THREADS];
-	const RmScan S = V.scan[K];
-	for (uint32_t t = blockIdx.x; t < S.n_tiles; t += gridDim.x) {
-		const rm_u64 i0 = (rm_u64)t * RM_TILE + (rm_u64)threadIdx.x * RM_ITEMS;
-		for (uint32_t q = 0; q < S.n_q; ++q) {
-			rm_u64 v = 0, total;
-			for (int k = 0; k < RM_ITEMS; ++k) if (i0 + k < S.n) v += rm_value<K>(V, (int)q, i0 + k);
-			rm_block_excl(v, s, total);
-			if (threadIdx.x == 0) S.tile_sum[(rm_u64)q * S.n_tiles + t] = total;
-		}
-	}
-}
-// ONE workgroup: tile_off[q][t] = what the tiles before t add; tile_off[q][n_tiles] = off[q][n] = the total
-template <int K> static __global__ __launch_bounds__(RM_THREADS) void k_remove_tile_scan(RmDev V)
-{
-	__shared__ rm_u64 s[RM_THREADS];
-	const RmScan S = V.scan[K];
-	for (uint32_t q = 0; q < S.n_q; ++q) {
-		rm_u64 run = 0;
-		for (uint32_t t0 = 0; t0 < S.n_tiles; t0 += RM_THREADS) {
-			const uint32_t t = t0 + threadIdx.x;
-			const rm_u64 v = t < S.n_tiles ? S.tile_sum[(rm_u64)q * S.n_tiles + t] : 0ULL;
-			rm_u64 total;
-			const rm_u64 before = rm_block_excl(v, s, total);
-			if (t < S.n_tiles) S.tile_off[(rm_u64)q * (S.n_tiles + 1) + t] = run + before;
-			run += total;
-		}
-		if (threadIdx.x == 0) { S.tile_off[(rm_u64)q * (S.n_tiles + 1) + S.n_tiles] = run; S.off[(rm_u64)q * (S.n + 1) + S.n] = run; }
-	}
-}
-template <int K> static __global__ __launch_bounds__(RM_THREADS) void k_remove_offsets(RmDev V)
-{
-	__shared__ rm_u64 s[RM_THREADS];
-	const RmScan S = V.scan[K];
-	for (uint32_t t = blockIdx.x; t < S.n_tiles; t += gridDim.x) {
-		const rm_u64 i0 = (rm_u64)t * RM_TILE + (rm_u64)threadIdx.x * RM_ITEMS;
-		for (uint32_t q = 0; q < S.n_q; ++q) {
-			rm_u64 c[RM_ITEMS], v = 0, total;
-			for (int k = 0; k < RM_ITEMS; ++k) { c[k] = i0 + k < S.n ? rm_value<K>(V, (int)q, i0 + k) : 0ULL; v += c[k]; }
-			rm_u64 at = S.tile_off[(rm_u64)q * (S.n_tiles + 1) + t] + rm_block_excl(v, s, total);
-			for (int k = 0; k < RM_ITEMS && i0 + k < S.n; ++k) { S.off[(rm_u64)q * (S.n + 1) + i0 + k] = at; at += c[k]; }
-		}
-	}
-}
+// ---------------------------------------------------------------- 2. the scans: k_ts_sums / _scan / _offsets of pga_tile_scan.h
 
 // ---------------------------------------------------------------- 3. behind the member scan: blocks, members, nodes
 // a block keeps its index and its id; without a kept member it is dead as pga_plan_simplify leaves a dead block
 static __global__ __launch_bounds__(RM_THREADS) void k_remove_blocks(RmDev V)
 {
-	const rm_u64 *kept = rm_off(V.scan[RM_SCAN_MEMBERS], RM_Q_KEPT);
+	const rm_u64 *kept = ts_off(V.scan[RM_SCAN_MEMBERS], RM_Q_KEPT);
 	for (uint64_t b = (uint64_t)blockIdx.x * RM_THREADS + threadIdx.x; b < V.n_blocks; b += (uint64_t)gridDim.x * RM_THREADS) {
 		const pga_topo_block_t B = V.blocks[b];
 		const uint32_t n = (uint32_t)(kept[V.slot_first[b + 1]] - kept[V.slot_first[b]]);
@@ -151,7 +82,7 @@ static __global__ __launch_bounds__(RM_THREADS) void k_remove_blocks(RmDev V)
 }
 static __global__ __launch_bounds__(RM_THREADS) void k_remove_members(RmDev V)
 {
-	const rm_u64 *kept = rm_off(V.scan[RM_SCAN_MEMBERS], RM_Q_KEPT);
+	const rm_u64 *kept = ts_off(V.scan[RM_SCAN_MEMBERS], RM_Q_KEPT);
 	for (uint64_t m = (uint64_t)blockIdx.x * RM_THREADS + threadIdx.x; m < V.n_members; m += (uint64_t)gridDim.x * RM_THREADS) {
 		if (V.mkeep[m]) V.o_members[kept[m]] = V.members[m];
 		V.member_map[m] = V.mkeep[m] ? (long long)kept[m] : -1LL;
@@ -160,7 +91,7 @@ static __global__ __launch_bounds__(RM_THREADS) void k_remove_members(RmDev V)
 // one thread per position: a node of a kept path goes to its place; its member is its rank among the kept members of its block
 static __global__ __launch_bounds__(RM_THREADS) void k_remove_nodes(RmDev V)
 {
-	const rm_u64 *kept = rm_off(V.scan[RM_SCAN_MEMBERS], RM_Q_KEPT);
+	const rm_u64 *kept = ts_off(V.scan[RM_SCAN_MEMBERS], RM_Q_KEPT);
 	for (uint64_t i = (uint64_t)blockIdx.x * RM_THREADS + threadIdx.x; i < V.n_nodes; i += (uint64_t)gridDim.x * RM_THREADS) {
 		const uint32_t p = V.path_of[i];
 		if (!V.keep[p]) continue;
@@ -188,15 +119,15 @@ template <int LIST> static __global__ __launch_bounds__(RM_THREADS) void k_remov
 {
 	__shared__ rm_u64 s_rng[2];
 	const RmScan S = V.scan[RM_SCAN_MEMBERS];
-	const rm_u64 *in = rm_off(S, RM_Q_IN_SUB + LIST), *out = rm_off(S, RM_Q_OUT_SUB + LIST);
+	const rm_u64 *in = ts_off(S, RM_Q_IN_SUB + LIST), *out = ts_off(S, RM_Q_OUT_SUB + LIST);
 	const rm_u64 n = out[S.n], n_tiles = (n + RM_TILE - 1) / RM_TILE;
 	for (rm_u64 t = blockIdx.x; t < n_tiles; t += gridDim.x) {
 		const rm_u64 j0 = t * RM_TILE, j1 = j0 + RM_TILE < n ? j0 + RM_TILE : n;
-		if (threadIdx.x < 2) s_rng[threadIdx.x] = rm_last_le(out, 0, S.n, threadIdx.x ? j1 - 1 : j0);
+		if (threadIdx.x < 2) s_rng[threadIdx.x] = ts_last_le(out, 0, S.n, threadIdx.x ? j1 - 1 : j0);
 		__syncthreads();
 		const rm_u64 lo = s_rng[0], hi = s_rng[1] + 1;
 		for (rm_u64 j = j0 + threadIdx.x; j < j1; j += RM_THREADS) {
-			const rm_u64 m = rm_last_le(out, lo, hi, j);
+			const rm_u64 m = ts_last_le(out, lo, hi, j);
 			rm_copy_one<LIST>(V, j, in[m] + (j - out[m]));
 		}
 		__syncthreads();
@@ -209,15 +140,15 @@ static __global__ __launch_bounds__(RM_THREADS) void k_remove_letters(RmDev V)
 {
 	__shared__ rm_u64 s_rng[2];
 	const RmScan S = V.scan[RM_SCAN_LETTERS];
-	const rm_u64 *out = rm_off(S, 0);
+	const rm_u64 *out = ts_off(S, 0);
 	const rm_u64 n = out[S.n], n_tiles = (n + RM_TILE - 1) / RM_TILE;
 	for (rm_u64 t = blockIdx.x; t < n_tiles; t += gridDim.x) {
 		const rm_u64 j0 = t * RM_TILE, j1 = j0 + RM_TILE < n ? j0 + RM_TILE : n;
-		if (threadIdx.x < 2) s_rng[threadIdx.x] = rm_last_le(out, 0, S.n, threadIdx.x ? j1 - 1 : j0);
+		if (threadIdx.x < 2) s_rng[threadIdx.x] = ts_last_le(out, 0, S.n, threadIdx.x ? j1 - 1 : j0);
 		__syncthreads();
 		const rm_u64 lo = s_rng[0], hi = s_rng[1] + 1;
 		for (rm_u64 j = j0 + threadIdx.x; j < j1; j += RM_THREADS) {
-			const rm_u64 k = rm_last_le(out, lo, hi, j);
+			const rm_u64 k = ts_last_le(out, lo, hi, j);
 			V.o_ins_seq[j] = V.ins_seq[V.o_inss[k].seq_off + (j - out[k])];
 		}
 		__syncthreads();
@@ -227,7 +158,7 @@ static __global__ __launch_bounds__(RM_THREADS) void k_remove_letters(RmDev V)
 static __global__ __launch_bounds__(RM_THREADS) void k_remove_seq_off(RmDev V)
 {
 	const RmScan S = V.scan[RM_SCAN_LETTERS];
-	const rm_u64 *out = rm_off(S, 0);
+	const rm_u64 *out = ts_off(S, 0);
 	for (rm_u64 k = (rm_u64)blockIdx.x * RM_THREADS + threadIdx.x; k < S.n; k += (rm_u64)gridDim.x * RM_THREADS) V.o_inss[k].seq_off = out[k];
 }
 

@@ -18,34 +18,14 @@
 // Everything is queued on one stream and the call waits once.  With a batch, the matches whose bit plane is not empty are known only after
 // that wait: their letters are staged, counted, and the lists are built a second time.  The index arithmetic is pga_reweave_idx.h.
 #include "pga_common.h"
+#include "pga_graph_host.h"
 #include "../../include/pga_align.h"
 #include "pga_reweave_idx.h"
 #include "pga_runs.h"
-#include <rocprim/rocprim.hpp>
 
 namespace pga {
 
-template <class T> static void rw_excl_scan(const T *in, T *out, size_t n, hipStream_t st)
-{
-	size_t tb = 0;
-	PGA_HIP(rocprim::exclusive_scan(nullptr, tb, in, out, (T)0, n, rocprim::plus<T>(), st));
-	DBuf<uint8_t> tmp(tb + 16);
-	PGA_HIP(rocprim::exclusive_scan(tmp.p, tb, in, out, (T)0, n, rocprim::plus<T>(), st));
-}
-template <class K> static void rw_sort_pairs(K *kin, K *kout, uint32_t *vin, uint32_t *vout, size_t n, int bits, hipStream_t st)
-{
-	size_t tb = 0;
-	PGA_HIP(rocprim::radix_sort_pairs(nullptr, tb, kin, kout, vin, vout, n, 0, bits, st));
-	DBuf<uint8_t> tmp(tb + 16);
-	PGA_HIP(rocprim::radix_sort_pairs(tmp.p, tb, kin, kout, vin, vout, n, 0, bits, st));
-}
-template <class T> static T *rw_host_array(uint64_t n)
-{
-	T *p = (T*)calloc((size_t)(n ? n : 1), sizeof(T));
-	if (!p) throw std::runtime_error("pga_plan_merge: out of host memory");
-	return p;
-}
-static unsigned rw_grid(uint64_t items, uint64_t per_block) { return (unsigned)std::min<uint64_t>(std::max<uint64_t>((items + per_block - 1) / per_block, 1), 2048); }
+static unsigned rw_grid(uint64_t items, uint64_t per_block) { return grid_for(items, per_block, 2048); }
 static int rw_bits(uint64_t n) { int b = 1; while (b < 64 && (n >> b)) ++b; return b; }
 
 void plan_merge_host(int32_t n_groups, const int64_t *group_off, const pga_plan_block_t *blocks, int64_t n_matches, const pga_match_t *matches, const uint32_t *cigars,
@@ -58,12 +38,12 @@ void plan_merge_host(int32_t n_groups, const int64_t *group_off, const pga_plan_
 	if (n_matches == 0) return;
 	const uint64_t nm = (uint64_t)n_matches, nh = 2 * nm, n_hb = T.hb_block.size(), nb = T.blk.size();
 	const uint64_t cap_iv = 2 * nh + n_hb, cap_cig = T.cigar_in + 4 * nm;
-	out->matches = rw_host_array<pga_plan_match_t>(nm);
-	out->blocks = rw_host_array<pga_plan_block_res_t>(n_hb);
-	out->intervals = rw_host_array<pga_plan_interval_t>(cap_iv);
-	out->slice_intervals = rw_host_array<pga_slice_interval_t>(cap_iv);
-	out->promises = rw_host_array<pga_plan_promise_t>(nm);
-	out->cigars = rw_host_array<uint32_t>(cap_cig);
+	out->matches = host_array<pga_plan_match_t>(nm, "pga_plan_merge");
+	out->blocks = host_array<pga_plan_block_res_t>(n_hb, "pga_plan_merge");
+	out->intervals = host_array<pga_plan_interval_t>(cap_iv, "pga_plan_merge");
+	out->slice_intervals = host_array<pga_slice_interval_t>(cap_iv, "pga_plan_merge");
+	out->promises = host_array<pga_plan_promise_t>(nm, "pga_plan_merge");
+	out->cigars = host_array<uint32_t>(cap_cig, "pga_plan_merge");
 	// ---- the device ----
 	StreamLease stream;
 	hipStream_t st = stream.s;
@@ -130,17 +110,17 @@ void plan_merge_host(int32_t n_groups, const int64_t *group_off, const pga_plan_
 			hipLaunchKernelGGL(k_rw_mask, dim3(rw_grid(sides.size(), RW_WAVES)), dim3(RW_THREADS), 0, st, V, (const uint32_t*)d_sides.p, (uint64_t)sides.size());
 		if (!jobs.empty()) hipLaunchKernelGGL(k_rw_letters, dim3(rw_grid(jobs.size(), RW_WAVES)), dim3(RW_THREADS), 0, st, V, (const RwJob*)d_jobs.p, (uint64_t)jobs.size(), (const RwV4*)d_stage.p);
 		hipLaunchKernelGGL(k_rw_match, dim3(rw_grid(nm, RW_THREADS)), dim3(RW_THREADS), 0, st, V);
-		rw_sort_pairs(d_hkey.p, d_hkey2.p, d_hval.p, d_hs.p, nh, 32 + rw_bits(nb), st);
-		rw_sort_pairs(d_pkey.p, d_pkey2.p, d_pval.p, d_byid.p, nm, 64, st);
+		radix_sort_pairs(d_hkey.p, d_hkey2.p, d_hval.p, d_hs.p, nh, 32 + rw_bits(nb), st);
+		radix_sort_pairs(d_pkey.p, d_pkey2.p, d_pval.p, d_byid.p, nm, 64, st);
 		hipLaunchKernelGGL(k_rw_groups, dim3(rw_grid(nm, RW_THREADS)), dim3(RW_THREADS), 0, st, V, (const uint32_t*)d_byid.p);
-		rw_sort_pairs(d_pgrp.p, d_pgrp2.p, d_byid.p, d_pm.p, nm, rw_bits(T.n_groups), st);
+		radix_sort_pairs(d_pgrp.p, d_pgrp2.p, d_byid.p, d_pm.p, nm, rw_bits(T.n_groups), st);
 		hipLaunchKernelGGL(k_rw_hits, dim3(rw_grid(nh + 1, RW_THREADS)), dim3(RW_THREADS), 0, st, V);
-		rw_excl_scan(d_cntb.p, d_offb.p, nh + 1, st);
-		rw_excl_scan(d_cnta.p, d_offa.p, nh + 1, st);
+		excl_scan(d_cntb.p, d_offb.p, nh + 1, st);
+		excl_scan(d_cnta.p, d_offa.p, nh + 1, st);
 		hipLaunchKernelGGL(k_rw_intervals, dim3(rw_grid(nh, RW_THREADS)), dim3(RW_THREADS), 0, st, V);
 		hipLaunchKernelGGL(k_rw_blocks, dim3(rw_grid(n_hb, RW_THREADS)), dim3(RW_THREADS), 0, st, V);
 		hipLaunchKernelGGL(k_rw_cigar_plan, dim3(rw_grid(nm + 1, RW_THREADS)), dim3(RW_THREADS), 0, st, V);
-		rw_excl_scan(d_nout.p, d_coff.p, nm + 1, st);
+		excl_scan(d_nout.p, d_coff.p, nm + 1, st);
 		hipLaunchKernelGGL(k_rw_cigar_write, dim3(rw_grid(nm, RW_WAVES)), dim3(RW_THREADS), 0, st, V);
 		PGA_HIP(hipGetLastError());
 		// ---- the one wait ----

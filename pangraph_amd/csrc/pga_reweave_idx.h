@@ -15,6 +15,7 @@
 #include "pga_common.h"
 #endif
 #include "../../include/pga_align.h"
+#include "pga_xxh64.h"
 #include <algorithm>
 #include <stdexcept>
 #include <string>
@@ -73,36 +74,16 @@ __host__ __device__ inline uint32_t rw_popc(uint32_t x)
 #endif
 }
 
-// ---------------------------------------------------------------- XXH64 (seed 0) of n little-endian u64 words, n = 3 or 6
-__host__ __device__ inline uint64_t rw_rol(uint64_t x, int r) { return (x << r) | (x >> (64 - r)); }
-__host__ __device__ inline uint64_t rw_xxh64_words(const uint64_t *w, int n)
-{
-	const uint64_t P1 = 0x9E3779B185EBCA87ULL, P2 = 0xC2B2AE3D27D4EB4FULL, P3 = 0x165667B19E3779F9ULL, P4 = 0x85EBCA77C2B2AE63ULL, P5 = 0x27D4EB2F165667C5ULL;
-	uint64_t h; int at = 0;
-	if (n >= 4) {
-		uint64_t v0 = P1 + P2, v1 = P2, v2 = 0, v3 = 0 - P1;
-		for (; n - at >= 4; at += 4) {
-			v0 = rw_rol(v0 + w[at] * P2, 31) * P1; v1 = rw_rol(v1 + w[at + 1] * P2, 31) * P1;
-			v2 = rw_rol(v2 + w[at + 2] * P2, 31) * P1; v3 = rw_rol(v3 + w[at + 3] * P2, 31) * P1;
-		}
-		h = rw_rol(v0, 1) + rw_rol(v1, 7) + rw_rol(v2, 12) + rw_rol(v3, 18);
-		h = (h ^ (rw_rol(v0 * P2, 31) * P1)) * P1 + P4; h = (h ^ (rw_rol(v1 * P2, 31) * P1)) * P1 + P4;
-		h = (h ^ (rw_rol(v2 * P2, 31) * P1)) * P1 + P4; h = (h ^ (rw_rol(v3 * P2, 31) * P1)) * P1 + P4;
-	} else h = P5;
-	h += (uint64_t)n * 8;
-	for (; at < n; ++at) h = rw_rol(h ^ (rw_rol(w[at] * P2, 31) * P1), 27) * P1 + P4;
-	h ^= h >> 33; h *= P2; h ^= h >> 29; h *= P3; h ^= h >> 32;
-	return h;
-}
+// ---------------------------------------------------------------- the ids: XXH64 (pga_xxh64.h) of six and of three words
 __host__ __device__ inline uint64_t rw_match_id(uint64_t q_id, uint32_t qs, uint32_t qe, uint64_t r_id, uint32_t rs, uint32_t re)
 {
 	const uint64_t w[6] = {q_id, qs, qe, r_id, rs, re};
-	return rw_xxh64_words(w, 6);
+	return xxh64_words(w, 6);
 }
 __host__ __device__ inline uint64_t rw_gap_id(uint64_t block_id, uint32_t start, uint32_t end)
 {
 	const uint64_t w[3] = {block_id, start, end};
-	return rw_xxh64_words(w, 3);
+	return xxh64_words(w, 3);
 }
 
 // ---------------------------------------------------------------- the N counts, one wave per side

@@ -19,6 +19,8 @@
 //                     running count plus the number of lower lanes that go to the same interval -- list order is kept for any input order
 // All arithmetic is integer; atomic adds only feed sums and counts, so the result does not depend on the launch geometry.
 #include "pga_common.h"
+#include "pga_graph_host.h"
+#include "pga_wave.h"
 #include "../../include/pga_align.h"
 
 namespace pga {
@@ -230,12 +232,6 @@ __global__ __launch_bounds__(SL_THREADS) void k_slice_scan_local(SlDev V)
 	}
 }
 
-__device__ __forceinline__ sl_u64 sl_wave_incl(sl_u64 v, uint32_t lane)
-{
-#pragma unroll
-	for (int d = 1; d < 64; d <<= 1) { const sl_u64 o = __shfl_up(v, d); if ((int)lane >= d) v += o; }
-	return v;
-}
 // ONE wave: exclusive sums of the slice totals in slice order, the grand totals behind them, and the slice records of the output
 __global__ __launch_bounds__(64) void k_slice_scan_slices(SlDev V, pga_slice_res_t *out)
 {
@@ -246,7 +242,7 @@ __global__ __launch_bounds__(64) void k_slice_scan_slices(SlDev V, pga_slice_res
 		const bool ok = sl < V.n_slices;
 		SlTot t{0, 0, 0, 0, 0};
 		if (ok) t = V.slice_tot[sl];
-		const SlTot in{sl_wave_incl(t.kept, lane), sl_wave_incl(t.dropped, lane), sl_wave_incl(t.subs, lane), sl_wave_incl(t.dels, lane), sl_wave_incl(t.inss, lane)};
+		const SlTot in{wave_incl_u64(t.kept, lane), wave_incl_u64(t.dropped, lane), wave_incl_u64(t.subs, lane), wave_incl_u64(t.dels, lane), wave_incl_u64(t.inss, lane)};
 		if (ok) {
 			V.slice_base[sl] = SlTot{run.kept + in.kept - t.kept, run.dropped + in.dropped - t.dropped, run.subs + in.subs - t.subs, run.dels + in.dels - t.dels, run.inss + in.inss - t.inss};
 			pga_slice_res_t r; r.member_off = run.kept + in.kept - t.kept; r.n_kept = (uint32_t)t.kept; r.n_dropped = (uint32_t)t.dropped;
@@ -346,13 +342,14 @@ __global__ __launch_bounds__(SL_THREADS) void k_slice_write(SlDev V, pga_sub_t *
 }
 
 // ---------------------------------------------------------------- host side
+// (not host_array of pga_graph_host.h: these arrays are written in full and are not zeroed)
 template <class T> static T *sl_host_array(uint64_t n)
 {
 	T *p = (T*)malloc((size_t)(n ? n : 1) * sizeof(T));
 	if (!p) throw std::runtime_error("pga_slice_blocks: out of host memory");
 	return p;
 }
-static unsigned sl_grid(uint64_t items, uint64_t per_block) { return (unsigned)std::min<uint64_t>(std::max<uint64_t>((items + per_block - 1) / per_block, 1), 1u << 18); }
+static unsigned sl_grid(uint64_t items, uint64_t per_block) { return grid_for(items, per_block, 1u << 18); }
 
 void slice_blocks_host(int64_t n_blocks, const pga_slice_block_t *blocks, const pga_slice_interval_t *intervals, const pga_rc_member_t *members, const pga_slice_node_t *nodes,
                        const pga_sub_t *subs, const pga_del_t *dels, const pga_ins_t *inss, pga_slice_out_t *out)

@@ -16,27 +16,13 @@
 // The kernels and the host tables are pga_topo_idx.h (no wave intrinsic: tests/emu/topo_emu.cpp runs them on the host).
 // All arithmetic is integer; atomics feed only counts and minima, so the result does not depend on the launch geometry.
 #include "pga_common.h"
+#include "pga_graph_host.h"
 #include "../../include/pga_align.h"
 #include "pga_topo_idx.h"
-#include <rocprim/rocprim.hpp>
 
 namespace pga {
 
-static void tp_excl_scan(const uint32_t *in, uint32_t *out, size_t n, hipStream_t st)
-{
-	size_t tb = 0;
-	PGA_HIP(rocprim::exclusive_scan(nullptr, tb, in, out, 0u, n, rocprim::plus<uint32_t>(), st));
-	DBuf<uint8_t> tmp(tb + 16);
-	PGA_HIP(rocprim::exclusive_scan(tmp.p, tb, in, out, 0u, n, rocprim::plus<uint32_t>(), st));
-}
-template <class T> static T *tp_host_array(uint64_t n)
-{
-	T *p = (T*)calloc((size_t)(n ? n : 1), sizeof(T));
-	if (!p) throw std::runtime_error("pga_plan_simplify: out of host memory");
-	return p;
-}
-static unsigned tp_grid(uint64_t items, uint64_t per_block) { return (unsigned)std::min<uint64_t>(std::max<uint64_t>((items + per_block - 1) / per_block, 1), 2048); }
-template <class T> static void tp_fetch(T *dst, const T *src, uint64_t n, hipStream_t st) { if (n) PGA_HIP(hipMemcpyAsync(dst, src, n * sizeof(T), hipMemcpyDeviceToHost, st)); }
+static unsigned tp_grid(uint64_t items, uint64_t per_block) { return grid_for(items, per_block, 2048); }
 
 void plan_simplify_host(int64_t n_blocks, const pga_topo_block_t *blocks, int64_t n_paths, const pga_topo_path_t *paths, int64_t n_nodes, const pga_topo_node_t *nodes,
                         int64_t n_sched, const pga_topo_sched_t *sched, uint32_t flags, pga_topo_out_t *out)
@@ -75,22 +61,17 @@ void plan_simplify_host(int64_t n_blocks, const pga_topo_block_t *blocks, int64_
 	const unsigned g_pos = tp_grid(nn + 1, TP_THREADS);
 	hipLaunchKernelGGL(k_topo_keys, dim3(g_pos), dim3(TP_THREADS), 0, st, V);
 	hipLaunchKernelGGL(k_topo_check, dim3(tp_grid(std::max(T.n_slots, nb), TP_THREADS)), dim3(TP_THREADS), 0, st, V);
-	{
-		size_t tb = 0;
-		PGA_HIP(rocprim::radix_sort_keys(nullptr, tb, d_key.p, d_skey.p, nn, 0, 64, st));
-		DBuf<uint8_t> tmp(tb + 16);
-		PGA_HIP(rocprim::radix_sort_keys(tmp.p, tb, d_key.p, d_skey.p, nn, 0, 64, st));
-	}
+	radix_sort_keys(d_key.p, d_skey.p, nn, 64, st);
 	hipLaunchKernelGGL(k_topo_heads, dim3(g_pos), dim3(TP_THREADS), 0, st, V);
-	tp_excl_scan(d_head.p, d_hoff.p, nn + 1, st);
+	excl_scan(d_head.p, d_hoff.p, nn + 1, st);
 	hipLaunchKernelGGL(k_topo_runs, dim3(g_pos), dim3(TP_THREADS), 0, st, V);
 	hipLaunchKernelGGL(k_topo_keep, dim3(g_pos), dim3(TP_THREADS), 0, st, V);
-	tp_excl_scan(d_keep.p, d_koff.p, nn + 1, st);
+	excl_scan(d_keep.p, d_koff.p, nn + 1, st);
 	hipLaunchKernelGGL(k_topo_compact, dim3(g_pos), dim3(TP_THREADS), 0, st, V);
 	PGA_HIP(hipGetLastError());
 	// ---- the first wait: the checks and the two list lengths; then the lists themselves ----
 	uint32_t err[TP_ERRS], n_runs = 0, n_trans = 0;
-	tp_fetch(err, d_err.p, TP_ERRS, st); tp_fetch(&n_runs, d_hoff.p + nn, 1, st); tp_fetch(&n_trans, d_koff.p + nn, 1, st);
+	fetch(err, d_err.p, TP_ERRS, st); fetch(&n_runs, d_hoff.p + nn, 1, st); fetch(&n_trans, d_koff.p + nn, 1, st);
 	PGA_HIP(sync_stream(st));
 	if (err[TP_E_DEPTH] != TP_NONE) tp_fail("the nodes of a block do not sum to its depth (block " + std::to_string(err[TP_E_DEPTH]) + ")");
 	if (err[TP_E_SLOT] != TP_NONE) {
@@ -103,12 +84,12 @@ void plan_simplify_host(int64_t n_blocks, const pga_topo_block_t *blocks, int64_
 	{
 		Downloads dl(st);
 		dl.add(trans, (const pga_topo_edge_t*)d_trans.p, n_trans);
-		if (flags & PGA_TOPO_COUNTS) { out->edge_counts = tp_host_array<pga_topo_edge_t>(n_runs); tp_fetch(out->edge_counts, (const pga_topo_edge_t*)d_counts.p, n_runs, st); }
+		if (flags & PGA_TOPO_COUNTS) { out->edge_counts = host_array<pga_topo_edge_t>(n_runs, "pga_plan_simplify"); fetch(out->edge_counts, (const pga_topo_edge_t*)d_counts.p, n_runs, st); }
 		dl.wait();
 		PGA_HIP(sync_stream(st));
 	}
 	out->n_counts = (flags & PGA_TOPO_COUNTS) ? n_runs : 0;
-	out->transitive = tp_host_array<pga_topo_edge_t>(n_trans);
+	out->transitive = host_array<pga_topo_edge_t>(n_trans, "pga_plan_simplify");
 	if (n_trans) memcpy(out->transitive, trans.data(), n_trans * sizeof(pga_topo_edge_t));
 	out->n_transitive = n_trans;
 	// ---- the round ----
@@ -116,13 +97,13 @@ void plan_simplify_host(int64_t n_blocks, const pga_topo_block_t *blocks, int64_
 	if (flags & PGA_TOPO_EDGES_ONLY) return;
 	tp_choose(n_blocks, blocks, trans.data(), n_trans, n_sched, sched, R);
 	const uint64_t n_round = R.round.size(), n_partner = R.n_partner;
-	out->round = tp_host_array<pga_topo_round_t>(n_round);
+	out->round = host_array<pga_topo_round_t>(n_round, "pga_plan_simplify");
 	if (n_round == 0) return;
 	memcpy(out->round, R.round.data(), n_round * sizeof(pga_topo_round_t));
 	out->n_round = (int64_t)n_round; out->n_partner = (int64_t)n_partner;
-	out->partner = tp_host_array<uint32_t>(n_partner); out->new_nodes = tp_host_array<pga_topo_node_t>(n_partner);
-	out->old_left = tp_host_array<uint64_t>(n_partner); out->old_right = tp_host_array<uint64_t>(n_partner);
-	out->blocks = tp_host_array<pga_topo_block_t>(nb); out->paths = tp_host_array<pga_topo_path_t>(np);
+	out->partner = host_array<uint32_t>(n_partner, "pga_plan_simplify"); out->new_nodes = host_array<pga_topo_node_t>(n_partner, "pga_plan_simplify");
+	out->old_left = host_array<uint64_t>(n_partner, "pga_plan_simplify"); out->old_right = host_array<uint64_t>(n_partner, "pga_plan_simplify");
+	out->blocks = host_array<pga_topo_block_t>(nb, "pga_plan_simplify"); out->paths = host_array<pga_topo_path_t>(np, "pga_plan_simplify");
 	tp_blocks_after(n_blocks, blocks, R, out->blocks);
 	// ---- the pairing and the splice ----
 	const uint32_t n_tiles = (uint32_t)((nn + TP_TILE - 1) / TP_TILE);
@@ -143,13 +124,13 @@ void plan_simplify_host(int64_t n_blocks, const pga_topo_block_t *blocks, int64_
 	PGA_HIP(hipGetLastError());
 	// every pair drops one node: the size of the node list is known without asking the device; its own count is held against it
 	const uint64_t n_out = nn - n_partner;
-	out->nodes = tp_host_array<pga_topo_node_t>(n_out);
+	out->nodes = host_array<pga_topo_node_t>(n_out, "pga_plan_simplify");
 	uint32_t total = 0;
-	tp_fetch(&total, (const uint32_t*)d_toff.p + n_tiles, 1, st);
-	tp_fetch(out->partner, (const uint32_t*)d_partner.p, n_partner, st); tp_fetch(out->new_nodes, (const pga_topo_node_t*)d_new.p, n_partner, st);
-	tp_fetch(out->old_left, (const uint64_t*)d_left.p, n_partner, st); tp_fetch(out->old_right, (const uint64_t*)d_right.p, n_partner, st);
-	tp_fetch(out->paths, (const pga_topo_path_t*)d_opaths.p, np, st);
-	tp_fetch(out->nodes, (const pga_topo_node_t*)d_onodes.p, n_out, st);   // (the splice writes at most n_nodes entries whatever it counted: d_onodes holds them)
+	fetch(&total, (const uint32_t*)d_toff.p + n_tiles, 1, st);
+	fetch(out->partner, (const uint32_t*)d_partner.p, n_partner, st); fetch(out->new_nodes, (const pga_topo_node_t*)d_new.p, n_partner, st);
+	fetch(out->old_left, (const uint64_t*)d_left.p, n_partner, st); fetch(out->old_right, (const uint64_t*)d_right.p, n_partner, st);
+	fetch(out->paths, (const pga_topo_path_t*)d_opaths.p, np, st);
+	fetch(out->nodes, (const pga_topo_node_t*)d_onodes.p, n_out, st);   // (the splice writes at most n_nodes entries whatever it counted: d_onodes holds them)
 	PGA_HIP(sync_stream(st));
 	for (uint64_t e = 0; e < n_round; ++e) for (uint64_t k = 0; k < trans[R.round[e].transitive].count; ++k)
 		if (out->partner[R.round[e].partner_off + k] == TP_NONE) tp_fail("a slot of a partner list was left unwritten (round edge " + std::to_string(e) + ", member " + std::to_string(k) + ")");

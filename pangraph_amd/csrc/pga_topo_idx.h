@@ -2,7 +2,8 @@
 // find_transitive_edges / count_edges, merge_blocks.rs:33-89 orient_merging_edge / find_node_pairings, :196-234 graph_merging_update_paths /
 // _nodes).  None of it uses a wave intrinsic -- the block scan goes through LDS and barriers -- so all of this compiles under hipcc and, with
 // dev/emu/hip_emu.h included first, under g++ -std=c++17 -DPGA_EMU (tests/emu/topo_emu.cpp runs it against a direct scalar construction).
-// The radix sort of the keys and the two scans over run heads are rocPRIM's (pga_topo.hip) and are not in here.
+// The radix sort of the keys and the two scans over run heads are rocPRIM's (pga_topo.hip) and are not in here; the workgroup scan of the
+// splice is ts_block_excl of pga_tile_scan.h over 32 bits, the node hash is xxh64_words of pga_xxh64.h.
 // pga_apply_idx.h includes this header for the path lookup, the node hash and the splice: the kernels are static, one copy per translation unit.
 //
 // A POSITION is an index into nodes[] (path after path).  Its SUCCESSOR is the next position of its path, the path's first position behind
@@ -19,6 +20,8 @@
 #include "pga_common.h"
 #endif
 #include "../../include/pga_align.h"
+#include "pga_tile_scan.h"
+#include "pga_xxh64.h"
 #include <algorithm>
 #include <cstring>
 #include <stdexcept>
@@ -28,7 +31,7 @@
 namespace pga {
 
 typedef unsigned long long tp_u64;
-constexpr int TP_THREADS = 256, TP_ITEMS = 4, TP_TILE = TP_THREADS * TP_ITEMS;
+constexpr int TP_THREADS = TS_THREADS, TP_ITEMS = TS_ITEMS, TP_TILE = TS_TILE;
 static_assert(TP_TILE == PGA_TOPO_TILE, "the header exports the tile of the splice");
 constexpr uint32_t TP_NONE = 0xffffffffu;
 constexpr tp_u64 TP_NOKEY = ~0ULL;
@@ -88,19 +91,10 @@ __host__ __device__ inline uint32_t tp_pred(const pga_topo_path_t &P, uint64_t i
 }
 
 // PangraphNode::new(None, block, path, strand, position): XXH64, seed 0, of five little-endian u64 words
-__host__ __device__ inline uint64_t tp_rol(uint64_t x, int r) { return (x << r) | (x >> (64 - r)); }
 __host__ __device__ inline uint64_t tp_node_id(uint64_t block_id, uint64_t path_id, uint64_t reverse, uint64_t pos0, uint64_t pos1)
 {
-	const uint64_t P1 = 0x9E3779B185EBCA87ULL, P2 = 0xC2B2AE3D27D4EB4FULL, P3 = 0x165667B19E3779F9ULL, P4 = 0x85EBCA77C2B2AE63ULL;
-	const uint64_t v0 = tp_rol(P1 + P2 + block_id * P2, 31) * P1, v1 = tp_rol(P2 + path_id * P2, 31) * P1;
-	const uint64_t v2 = tp_rol(reverse * P2, 31) * P1, v3 = tp_rol(0 - P1 + pos0 * P2, 31) * P1;
-	uint64_t h = tp_rol(v0, 1) + tp_rol(v1, 7) + tp_rol(v2, 12) + tp_rol(v3, 18);
-	h = (h ^ (tp_rol(v0 * P2, 31) * P1)) * P1 + P4; h = (h ^ (tp_rol(v1 * P2, 31) * P1)) * P1 + P4;
-	h = (h ^ (tp_rol(v2 * P2, 31) * P1)) * P1 + P4; h = (h ^ (tp_rol(v3 * P2, 31) * P1)) * P1 + P4;
-	h += 40;
-	h = tp_rol(h ^ (tp_rol(pos1 * P2, 31) * P1), 27) * P1 + P4;
-	h ^= h >> 33; h *= P2; h ^= h >> 29; h *= P3; h ^= h >> 32;
-	return h;
+	const uint64_t w[5] = {block_id, path_id, reverse, pos0, pos1};
+	return xxh64_words(w, 5);
 }
 
 // ---------------------------------------------------------------- 1. edge keys and the slot counts, one thread per position
@@ -207,23 +201,7 @@ static __global__ __launch_bounds__(TP_THREADS) void k_topo_pair(TpDev V)
 }
 
 // ---------------------------------------------------------------- 5. the splice
-// exclusive sums of one value per thread over the workgroup, through LDS; total: the workgroup's sum
-__device__ inline uint32_t tp_block_excl(uint32_t v, uint32_t *s, uint32_t &total)
-{
-	const uint32_t t = threadIdx.x;
-	s[t] = v;
-	__syncthreads();
-	for (uint32_t d = 1; d < (uint32_t)TP_THREADS; d <<= 1) {
-		const uint32_t x = t >= d ? s[t - d] : 0u;
-		__syncthreads();
-		s[t] += x;
-		__syncthreads();
-	}
-	total = s[TP_THREADS - 1];
-	const uint32_t before = s[t] - v;
-	__syncthreads();
-	return before;
-}
+// the workgroup scan is ts_block_excl of pga_tile_scan.h, over 32 bits (the buffers are part of TpDev)
 static __global__ __launch_bounds__(TP_THREADS) void k_topo_tile_sums(TpDev V)
 {
 	__shared__ uint32_t s[TP_THREADS];
@@ -231,7 +209,7 @@ static __global__ __launch_bounds__(TP_THREADS) void k_topo_tile_sums(TpDev V)
 		const uint64_t i0 = (uint64_t)t * TP_TILE + (uint64_t)threadIdx.x * TP_ITEMS;
 		uint32_t v = 0, total;
 		for (int q = 0; q < TP_ITEMS; ++q) if (i0 + q < V.n_nodes) v += V.cnt[i0 + q];
-		tp_block_excl(v, s, total);
+		ts_block_excl(v, s, total);
 		if (threadIdx.x == 0) V.tile_sum[t] = total;
 	}
 }
@@ -243,7 +221,7 @@ static __global__ __launch_bounds__(TP_THREADS) void k_topo_tile_scan(TpDev V)
 	for (uint32_t t0 = 0; t0 < V.n_tiles; t0 += TP_THREADS) {
 		const uint32_t t = t0 + threadIdx.x, v = t < V.n_tiles ? V.tile_sum[t] : 0u;
 		uint32_t total;
-		const uint32_t before = tp_block_excl(v, s, total);
+		const uint32_t before = ts_block_excl(v, s, total);
 		if (t < V.n_tiles) V.tile_off[t] = run + before;
 		run += total;
 	}
@@ -256,7 +234,7 @@ static __global__ __launch_bounds__(TP_THREADS) void k_topo_splice(TpDev V)
 		const uint64_t i0 = (uint64_t)t * TP_TILE + (uint64_t)threadIdx.x * TP_ITEMS;
 		uint32_t c[TP_ITEMS], v = 0, total;
 		for (int q = 0; q < TP_ITEMS; ++q) { c[q] = i0 + q < V.n_nodes ? V.cnt[i0 + q] : 0u; v += c[q]; }
-		uint32_t at = V.tile_off[t] + tp_block_excl(v, s, total);
+		uint32_t at = V.tile_off[t] + ts_block_excl(v, s, total);
 		for (int q = 0; q < TP_ITEMS; ++q) {
 			const uint64_t i = i0 + q;
 			if (i >= V.n_nodes) break;

@@ -126,6 +126,14 @@ __device__ __forceinline__ uint32_t wave_prefix_sum_incl(uint32_t v)
 	return v;
 }
 
+// inclusive prefix sum of a 64-bit value over the wave (lane order), by shuffles: what the one-wave scans of the graph entries use
+__device__ __forceinline__ unsigned long long wave_incl_u64(unsigned long long v, uint32_t lane)
+{
+#pragma unroll
+	for (int d = 1; d < 64; d <<= 1) { const unsigned long long o = __shfl_up(v, d); if ((int)lane >= d) v += o; }
+	return v;
+}
+
 // maximum of a signed 64-bit key over the wave; the result is uniform
 template <int CTRL, int ROW_MASK> __device__ __forceinline__ long long dpp_max_step_i64(long long v)
 {

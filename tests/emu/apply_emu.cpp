@@ -104,7 +104,7 @@ static uint64_t hash_words(std::initializer_list<uint64_t> w)
 {
 	std::vector<uint8_t> b;
 	for (uint64_t x : w) for (int i = 0; i < 8; ++i) b.push_back((uint8_t)(x >> (8 * i)));
-	return dt_xxh64(b.data(), b.size(), 0);
+	return xxh64_bytes(b.data(), b.size(), 0);
 }
 static Out direct(const Case &G)
 {

@@ -223,12 +223,11 @@ struct ScanBufs {
 	ScanBufs(uint64_t n, uint32_t n_q) : tile_sum((size_t)n_q * ((n + AS_TILE - 1) / AS_TILE)), tile_off((size_t)n_q * ((n + AS_TILE - 1) / AS_TILE + 1)), off((size_t)n_q * (n + 1)),
 		S{n, (uint32_t)((n + AS_TILE - 1) / AS_TILE), n_q, tile_sum.get(), tile_off.get(), off.get()} {}
 };
-template <int K> static void scan(const AsDev &V, unsigned grid)
+template <class Val> static void scan(const RmScan &S, const Val &val, unsigned grid)
 {
-	const uint32_t n_tiles = V.scan[K].n_tiles;
-	if (n_tiles) emu_launch(dim3(std::min<unsigned>(grid, n_tiles)), dim3(AS_THREADS), [&] { k_assemble_tile_sums<K>(V); });
-	emu_launch(dim3(1), dim3(AS_THREADS), [&] { k_assemble_tile_scan<K>(V); });
-	if (n_tiles) emu_launch(dim3(std::min<unsigned>(grid, n_tiles)), dim3(AS_THREADS), [&] { k_assemble_offsets<K>(V); });
+	if (S.n_tiles) emu_launch(dim3(std::min<unsigned>(grid, S.n_tiles)), dim3(AS_THREADS), [&] { k_ts_sums<as_u64, Val>(S, val); });
+	emu_launch(dim3(1), dim3(AS_THREADS), [&] { k_ts_scan<as_u64>(S); });
+	if (S.n_tiles) emu_launch(dim3(std::min<unsigned>(grid, S.n_tiles)), dim3(AS_THREADS), [&] { k_ts_offsets<as_u64, Val>(S, val); });
 }
 static void validate(const Case &G, uint32_t flags, AsTables &A, bool with_cut = true)
 {
@@ -266,11 +265,11 @@ static bool emulated(const Case &G, unsigned grid, uint32_t flags, uint64_t seq_
 	V.desc = desc.get(); V.o_members = omembers.get(); V.origin = origin.get();
 	V.nodes = nodes.get(); V.after_first = afirst.get(); V.after_depth = adepth.get(); V.who = who.get(); V.slot_cnt = slotcnt.get(); V.err = e.get();
 	V.scan[AS_SCAN_BEFORE] = b_before.S; V.scan[AS_SCAN_OUT] = b_out.S;
-	scan<AS_SCAN_BEFORE>(V, grid);
+	scan(V.scan[AS_SCAN_BEFORE], AsBeforeValue{V}, grid);
 	emu_launch(dim3(grid), dim3(AS_THREADS), [&] { k_assemble_desc(V); });
 	emu_launch(dim3(grid), dim3(AS_THREADS), [&] { k_assemble_who(V); });
 	emu_launch(dim3(grid), dim3(AS_THREADS), [&] { k_assemble_who_check(V); });
-	scan<AS_SCAN_OUT>(V, grid);
+	scan(V.scan[AS_SCAN_OUT], AsOutValue{V}, grid);
 	std::copy(e.get(), e.get() + AS_ERRS, err);
 	for (int i = 0; i < AS_ERRS; ++i) if (err[i] != AS_NONE) { refused = true; return true; }
 	const uint64_t ns_out = b_out.off[0 * (nmo + 1) + nmo], nd_out = b_out.off[1 * (nmo + 1) + nmo], ni_out = b_out.off[2 * (nmo + 1) + nmo];
@@ -281,7 +280,7 @@ static bool emulated(const Case &G, unsigned grid, uint32_t flags, uint64_t seq_
 	if (ni_out) emu_launch(dim3(grid), dim3(AS_THREADS), [&] { k_assemble_copy<RM_LIST_INS>(V); });
 	ScanBufs b_let(ni_out, 1);
 	V.scan[AS_SCAN_LETTERS] = b_let.S;
-	scan<AS_SCAN_LETTERS>(V, grid);
+	scan(V.scan[AS_SCAN_LETTERS], AsLetterValue{V}, grid);
 	std::copy(e.get(), e.get() + AS_ERRS, err);
 	for (int i = 0; i < AS_ERRS; ++i) if (err[i] != AS_NONE) { refused = true; return true; }
 	const uint64_t nl_out = b_let.off[ni_out];
@@ -340,21 +339,6 @@ int main()
 		Case G;
 		do G = generate(20, 4, 2, 0); while (G.cut.empty() || !pad_to(G, target));
 		if (direct(G, 0).M.size() != target || !run_case(G, 2, 0) || !run_case(G, 3, PGA_ASSEMBLE_MERGED_ONLY)) return 1;
-	}
-	// ---- the second level of the tile scan on its own: more tile sums than the one workgroup has threads, three quantities
-	{
-		const uint32_t n_tiles = 2 * AS_THREADS + 3;
-		Exact<as_u64> sums(3 * (size_t)n_tiles), offs(3 * ((size_t)n_tiles + 1)), off((size_t)6);
-		for (size_t i = 0; i < sums.n; ++i) sums[i] = rnd(5) ? rnd(1000) : (as_u64)rng() << 8;
-		AsDev V;
-		memset(&V, 0, sizeof(V));
-		V.scan[AS_SCAN_OUT] = RmScan{1, n_tiles, 3, sums.get(), offs.get(), off.get()};           // (n: only where the totals go)
-		emu_launch(dim3(1), dim3(AS_THREADS), [&] { k_assemble_tile_scan<AS_SCAN_OUT>(V); });
-		for (uint32_t q = 0; q < 3; ++q) {
-			as_u64 run = 0;
-			for (uint32_t t = 0; t <= n_tiles; ++t) { if (offs[(size_t)q * (n_tiles + 1) + t] != run) { fprintf(stderr, "assemble_emu: the tile scan is off at tile %u\n", t); return 1; } if (t < n_tiles) run += sums[(size_t)q * n_tiles + t]; }
-			if (off[q * 2 + 1] != run) { fprintf(stderr, "assemble_emu: the tile scan's total is off\n"); return 1; }
-		}
 	}
 	// ---- no cut: the input copied with compacted letters, no who; merged-only: nothing
 	g_case = -1;
@@ -434,9 +418,9 @@ int main()
 	{
 		X = H; AsTables A; validate(X, 0, A);
 		as_u64 err[AS_ERRS]; std::fill(err, err + AS_ERRS, AS_NONE);
-		uint64_t m = 0; while (A.blocks[rm_last_le(A.blk_first.data(), 0, A.blocks.size(), m)].kind != AS_K_MERGED) ++m;
+		uint64_t m = 0; while (A.blocks[ts_last_le(A.blk_first.data(), 0, A.blocks.size(), m)].kind != AS_K_MERGED) ++m;
 		err[AS_E_STATUS] = m;
-		const AsBlock &B = A.blocks[rm_last_le(A.blk_first.data(), 0, A.blocks.size(), m)];
+		const AsBlock &B = A.blocks[ts_last_le(A.blk_first.data(), 0, A.blocks.size(), m)];
 		std::string msg;
 		try { as_report(err, A, X.sl[B.ib].member_off + 0, X.sl.data()); } catch (std::runtime_error &e2) { msg = e2.what(); }
 		if (msg.find("promise " + std::to_string(B.promise) + ", member 0") == std::string::npos) { fprintf(stderr, "assemble_emu: the message is off: %s\n", msg.c_str()); return 1; }

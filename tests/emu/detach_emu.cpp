@@ -218,10 +218,10 @@ int main()
 {
 	// XXH64: the two values of the specification, and the stream of id((NodeId(2), "GGGGGGGG"))
 	std::vector<uint8_t> buf;
-	if (dt_xxh64((const uint8_t*)"", 0, 0) != 0xEF46DB3751D8E999ULL || dt_xxh64((const uint8_t*)"a", 1, 0) != 0xD24EC4F1A98C6E5BULL) { printf("XXH64 misses the specification's values\n"); return 1; }
+	if (xxh64_bytes((const uint8_t*)"", 0, 0) != 0xEF46DB3751D8E999ULL || xxh64_bytes((const uint8_t*)"a", 1, 0) != 0xD24EC4F1A98C6E5BULL) { printf("XXH64 misses the specification's values\n"); return 1; }
 	const uint64_t id = dt_block_id(2, "GGGGGGGG", 8, buf);
 	const uint8_t stream[24] = {2, 0, 0, 0, 0, 0, 0, 0, 8, 0, 0, 0, 0, 0, 0, 0, 'G', 'G', 'G', 'G', 'G', 'G', 'G', 'G'};
-	if (buf.size() != 24 || memcmp(buf.data(), stream, 24) || id != dt_xxh64(stream, 24, 0)) { printf("the block id stream\n"); return 1; }
+	if (buf.size() != 24 || memcmp(buf.data(), stream, 24) || id != xxh64_bytes(stream, 24, 0)) { printf("the block id stream\n"); return 1; }
 	if (run(edge_batch(), -1)) return 1;
 	const uint64_t edge_members = n_members, edge_orphans = n_orphans;
 	if (n_bad || n_gap) { printf("the edge batch holds a rejected orphan\n"); return 1; }

@@ -125,15 +125,16 @@ static Out direct(const Case &G, const pga_gfa_params_t &prm)
 
 // ---------------------------------------------------------------- the kernels in the order of pga_gfa.hip
 struct ScanBufs {
-	Exact<gf_u64> tile_sum, tile_off, off; GfScan S;
-	ScanBufs(const gf_u64 *val, uint64_t n) : tile_sum((n + GF_TILE - 1) / GF_TILE), tile_off((n + GF_TILE - 1) / GF_TILE + 1), off(n + 1),
-		S{n, (uint32_t)((n + GF_TILE - 1) / GF_TILE), 0, val, tile_sum.get(), tile_off.get(), off.get()} {}
+	Exact<gf_u64> tile_sum, tile_off, off; GfScan S; TsArray<gf_u64> val;
+	ScanBufs(const gf_u64 *val_, uint64_t n) : tile_sum((n + GF_TILE - 1) / GF_TILE), tile_off((n + GF_TILE - 1) / GF_TILE + 1), off(n + 1),
+		S{n, (uint32_t)((n + GF_TILE - 1) / GF_TILE), 1, tile_sum.get(), tile_off.get(), off.get()}, val{val_} {}
 };
-static void scan(const GfScan &S, unsigned grid)
+static void scan(const ScanBufs &B, unsigned grid)
 {
-	if (S.n_tiles) emu_launch(dim3(std::min<unsigned>(grid, S.n_tiles)), dim3(GF_THREADS), [&] { k_gfa_tile_sums(S); });
-	emu_launch(dim3(1), dim3(GF_THREADS), [&] { k_gfa_tile_scan(S); });
-	if (S.n_tiles) emu_launch(dim3(std::min<unsigned>(grid, S.n_tiles)), dim3(GF_THREADS), [&] { k_gfa_offsets(S); });
+	const GfScan &S = B.S;
+	if (S.n_tiles) emu_launch(dim3(std::min<unsigned>(grid, S.n_tiles)), dim3(GF_THREADS), [&] { k_ts_sums<gf_u64, TsArray<gf_u64>>(S, B.val); });
+	emu_launch(dim3(1), dim3(GF_THREADS), [&] { k_ts_scan<gf_u64>(S); });
+	if (S.n_tiles) emu_launch(dim3(std::min<unsigned>(grid, S.n_tiles)), dim3(GF_THREADS), [&] { k_ts_offsets<gf_u64, TsArray<gf_u64>>(S, B.val); });
 }
 
 // returns false on a CHECK; `refused`: the device checks stopped the call
@@ -168,7 +169,7 @@ static bool emulated(const Case &G, unsigned grid, const pga_gfa_params_t &prm, 
 	std::copy(key.get(), key.get() + nn, k1.get()); std::sort(k1.get(), k1.get() + nn);
 	emu_launch(dim3(grid), dim3(GF_THREADS), [&] { k_gfa_dupflags(V); });
 	emu_launch(dim3(grid), dim3(GF_THREADS), [&] { k_gfa_keep(V); });
-	scan(b_keep.S, grid);
+	scan(b_keep, grid);
 	emu_launch(dim3(grid), dim3(GF_THREADS), [&] { k_gfa_steps(V); });
 	emu_launch(dim3(grid), dim3(GF_THREADS), [&] { k_gfa_path_steps(V); });
 	V.lkey = k0.get(); V.lskey = k1.get(); V.head_off = hoff.get(); V.run_start = rstart.get();
@@ -195,7 +196,7 @@ static bool emulated(const Case &G, unsigned grid, const pga_gfa_params_t &prm, 
 	V.n_seg = n_seg; V.n_links = n_links; V.n_rows = n_rows; V.n_steps = n_steps; V.n_items = n_items;
 	V.segs = segs.get(); V.rows = rows.get(); V.len = len.get(); V.off = b_items.S.off; V.row_off = rowoff.get();
 	emu_launch(dim3(grid), dim3(GF_THREADS), [&] { k_gfa_lens(V); });
-	scan(b_items.S, grid);
+	scan(b_items, grid);
 	emu_launch(dim3(grid), dim3(GF_THREADS), [&] { k_gfa_row_off(V); });
 	const uint64_t n_bytes = b_items.off[n_items];
 	for (uint64_t k = 0; k < n_seg; ++k) H.segs[k].byte_off = b_items.off[2 + k];
@@ -279,17 +280,6 @@ int main()
 		if (E.text != want) { fprintf(stderr, "gfa_emu: the hand-made graph gives\n%s", E.text.c_str()); return 1; }
 		if (!run_case(G, 1, prm, {9})) return 1;
 	}
-	// ---- the second level of the tile scan on its own: more tile sums than the one workgroup has threads
-	{
-		const uint32_t n_tiles = 2 * GF_THREADS + 3;
-		Exact<gf_u64> sums(n_tiles), offs((size_t)n_tiles + 1), off(2);
-		for (size_t i = 0; i < sums.n; ++i) sums[i] = rnd(5) ? rnd(1000) : (gf_u64)rng() >> 12;
-		const GfScan S{1, n_tiles, 0, nullptr, sums.get(), offs.get(), off.get()};                  // (n: only where the total goes)
-		emu_launch(dim3(1), dim3(GF_THREADS), [&] { k_gfa_tile_scan(S); });
-		gf_u64 run = 0;
-		for (uint32_t t = 0; t <= n_tiles; ++t) { if (offs[t] != run) { fprintf(stderr, "gfa_emu: the tile scan is off at tile %u\n", t); return 1; } if (t < n_tiles) run += sums[t]; }
-		if (off[1] != run) { fprintf(stderr, "gfa_emu: the tile scan's total is off\n"); return 1; }
-	}
 	// ---- decimal widths at every edge
 	{
 		gf_u64 p = 1;
@@ -352,7 +342,7 @@ int main()
 	if (!ok) { fprintf(stderr, "gfa_emu: a refusal behind the first wait is off\n"); return 1; }
 	// ---- the lookup at its edges
 	const gf_u64 offs[6] = {0, 2, 2, 2, 5, 5};
-	if (gf_last_le(offs, 0, 5, 0) != 0 || gf_last_le(offs, 0, 5, 1) != 0 || gf_last_le(offs, 0, 5, 2) != 3 || gf_last_le(offs, 0, 5, 4) != 3 || gf_last_le(offs, 3, 4, 4) != 3) { fprintf(stderr, "gfa_emu: a lookup is off\n"); return 1; }
+	if (ts_last_le(offs, 0, 5, 0) != 0 || ts_last_le(offs, 0, 5, 1) != 0 || ts_last_le(offs, 0, 5, 2) != 3 || ts_last_le(offs, 0, 5, 4) != 3 || ts_last_le(offs, 3, 4, 4) != 3) { fprintf(stderr, "gfa_emu: a lookup is off\n"); return 1; }
 	printf("gfa_emu OK (%zu items cut by a tile edge, %zu nodes filtered, %zu graphs of more than two tiles)\n", n_cut, n_dropped, n_big);
 	return 0;
 }

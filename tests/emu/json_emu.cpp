@@ -209,15 +209,16 @@ static Out direct(const Case &G)
 
 // ---------------------------------------------------------------- the kernels in the order of pga_json.hip
 struct ScanBufs {
-	Exact<gf_u64> tile_sum, tile_off, off; GfScan S;
-	ScanBufs(const gf_u64 *val, uint64_t n) : tile_sum((n + GF_TILE - 1) / GF_TILE), tile_off((n + GF_TILE - 1) / GF_TILE + 1), off(n + 1),
-		S{n, (uint32_t)((n + GF_TILE - 1) / GF_TILE), 0, val, tile_sum.get(), tile_off.get(), off.get()} {}
+	Exact<gf_u64> tile_sum, tile_off, off; GfScan S; TsArray<gf_u64> val;
+	ScanBufs(const gf_u64 *val_, uint64_t n) : tile_sum((n + GF_TILE - 1) / GF_TILE), tile_off((n + GF_TILE - 1) / GF_TILE + 1), off(n + 1),
+		S{n, (uint32_t)((n + GF_TILE - 1) / GF_TILE), 1, tile_sum.get(), tile_off.get(), off.get()}, val{val_} {}
 };
-static void scan(const GfScan &S, unsigned grid)
+static void scan(const ScanBufs &B, unsigned grid)
 {
-	if (S.n_tiles) launch(dim3(std::min<unsigned>(grid, S.n_tiles)), dim3(GF_THREADS), [&] { k_gfa_tile_sums(S); }, true);
-	launch(dim3(1), dim3(GF_THREADS), [&] { k_gfa_tile_scan(S); }, true);
-	if (S.n_tiles) launch(dim3(std::min<unsigned>(grid, S.n_tiles)), dim3(GF_THREADS), [&] { k_gfa_offsets(S); }, true);
+	const GfScan &S = B.S;
+	if (S.n_tiles) launch(dim3(std::min<unsigned>(grid, S.n_tiles)), dim3(GF_THREADS), [&] { k_ts_sums<gf_u64, TsArray<gf_u64>>(S, B.val); }, true);
+	launch(dim3(1), dim3(GF_THREADS), [&] { k_ts_scan<gf_u64>(S); }, true);
+	if (S.n_tiles) launch(dim3(std::min<unsigned>(grid, S.n_tiles)), dim3(GF_THREADS), [&] { k_ts_offsets<gf_u64, TsArray<gf_u64>>(S, B.val); }, true);
 }
 static void validate(const Case &G, JsTables &J, uint32_t flags = 0)
 {
@@ -264,23 +265,23 @@ static bool emulated(const Case &G, unsigned grid, uint32_t chunk, const std::ve
 	{ std::vector<uint32_t> ix(nn); std::iota(ix.begin(), ix.end(), 0u); std::stable_sort(ix.begin(), ix.end(), [&](uint32_t a, uint32_t b) { return bk[a] < bk[b]; });
 	  for (uint64_t i = 0; i < nn; ++i) border[i] = order[ix[i]]; }
 	launch(dim3(grid), dim3(GF_THREADS), [&] { k_json_counts(V); });
-	scan(b_s.S, grid); scan(b_d.S, grid); scan(b_i.S, grid);
+	scan(b_s, grid); scan(b_d, grid); scan(b_i, grid);
 	launch(dim3(grid), dim3(GF_THREADS), [&] { k_json_chunks(V); });
-	scan(b_c.S, grid);
+	scan(b_c, grid);
 	launch(dim3(grid), dim3(GF_THREADS), [&] { k_json_check_subs(V); });
 	launch(dim3(grid), dim3(GF_THREADS), [&] { k_json_check_inss(V); });
 	js_report(te.get(), jerr.get());
 	CHECK(ns == nn);
 	js_bound(J, G.B.data(), nn, b_c.off[J.n_inss], chunk);
 	launch(dim3(grid), dim3(GF_THREADS), [&] { k_json_mitems(V); });
-	scan(b_m.S, grid);
+	scan(b_m, grid);
 	launch(dim3(grid), dim3(GF_THREADS), [&] { k_json_bstart(V); });
 	V.n_pitems = nn + 2 * np; V.n_bitems = 2 * na + b_m.off[ns]; V.n_items = 4 + V.n_pitems + V.n_bitems + nn;
 	Exact<gf_u64> len(V.n_items);
 	ScanBufs b_items(len.get(), V.n_items);
 	V.len = len.get(); V.off = b_items.S.off;
 	launch(dim3(grid), dim3(GF_THREADS), [&] { k_json_lens(V); });
-	scan(b_items.S, grid);
+	scan(b_items, grid);
 	launch(dim3(grid), dim3(GF_THREADS), [&] { k_json_offs(V); });
 	const uint64_t n_bytes = b_items.off[V.n_items];
 	O.sec = {4, b_items.off[1 + V.n_pitems] + (np ? 4 : 1) + 4, b_items.off[2 + V.n_pitems + V.n_bitems] + (na ? 4 : 1) + 4};

@@ -131,12 +131,11 @@ struct ScanBufs {
 	ScanBufs(uint64_t n, uint32_t n_q) : tile_sum((size_t)n_q * ((n + RM_TILE - 1) / RM_TILE)), tile_off((size_t)n_q * ((n + RM_TILE - 1) / RM_TILE + 1)), off((size_t)n_q * (n + 1)),
 		S{n, (uint32_t)((n + RM_TILE - 1) / RM_TILE), n_q, tile_sum.get(), tile_off.get(), off.get()} {}
 };
-template <int K> static void scan(const RmDev &V, unsigned grid)
+template <class Val> static void scan(const RmScan &S, const Val &val, unsigned grid)
 {
-	const uint32_t n_tiles = V.scan[K].n_tiles;
-	if (n_tiles) emu_launch(dim3(std::min<unsigned>(grid, n_tiles)), dim3(RM_THREADS), [&] { k_remove_tile_sums<K>(V); });
-	emu_launch(dim3(1), dim3(RM_THREADS), [&] { k_remove_tile_scan<K>(V); });
-	if (n_tiles) emu_launch(dim3(std::min<unsigned>(grid, n_tiles)), dim3(RM_THREADS), [&] { k_remove_offsets<K>(V); });
+	if (S.n_tiles) emu_launch(dim3(std::min<unsigned>(grid, S.n_tiles)), dim3(RM_THREADS), [&] { k_ts_sums<rm_u64, Val>(S, val); });
+	emu_launch(dim3(1), dim3(RM_THREADS), [&] { k_ts_scan<rm_u64>(S); });
+	if (S.n_tiles) emu_launch(dim3(std::min<unsigned>(grid, S.n_tiles)), dim3(RM_THREADS), [&] { k_ts_offsets<rm_u64, Val>(S, val); });
 }
 
 // returns false on a CHECK; `refused` says whether the device checks stopped the call (nothing behind them has run then)
@@ -172,7 +171,7 @@ static bool emulated(const Case &G, unsigned grid, uint32_t flags, bool null_seq
 	emu_launch(dim3(grid), dim3(TP_THREADS), [&] { k_topo_keys(T); });
 	emu_launch(dim3(grid), dim3(TP_THREADS), [&] { k_topo_check(T); });
 	emu_launch(dim3(grid), dim3(RM_THREADS), [&] { k_remove_mark(V); });
-	scan<RM_SCAN_MEMBERS>(V, grid);
+	scan(V.scan[RM_SCAN_MEMBERS], RmMemberValue{V}, grid);
 	std::copy(te.get(), te.get() + TP_ERRS, terr); std::copy(e.get(), e.get() + RM_ERRS, err);
 	for (int i = 0; i < TP_ERRS; ++i) if (terr[i] != TP_NONE) { refused = true; return true; }
 	const rm_u64 *tot = b_mem.off.get();
@@ -192,7 +191,7 @@ static bool emulated(const Case &G, unsigned grid, uint32_t flags, bool null_seq
 	std::unique_ptr<Exact<char>> oseq;
 	if (flags & PGA_REMOVE_COMPACT_LETTERS) {
 		V.scan[RM_SCAN_LETTERS] = b_let.S;
-		scan<RM_SCAN_LETTERS>(V, grid);
+		scan(V.scan[RM_SCAN_LETTERS], RmLetterValue{V}, grid);
 		std::copy(e.get(), e.get() + RM_ERRS, err);
 		for (int i = 0; i < RM_ERRS; ++i) if (err[i] != RM_NONE) { refused = true; return true; }
 		nl_out = b_let.off[ni_out];
@@ -239,21 +238,6 @@ int main()
 	if (n_big < 1 || n_dies < 5 || n_removed < 100 || n_long < 1) {
 		fprintf(stderr, "remove_emu: the generator lost its cases (%zu big, %zu blocks die, %zu members removed, %zu long lists)\n", n_big, n_dies, n_removed, n_long);
 		return 1;
-	}
-	// ---- the second level of the tile scan on its own: more tile sums than the one workgroup has threads, two quantities
-	{
-		const uint32_t n_tiles = 2 * RM_THREADS + 3;
-		Exact<rm_u64> sums(2 * (size_t)n_tiles), offs(2 * ((size_t)n_tiles + 1)), off(2 * 2);
-		for (size_t i = 0; i < sums.n; ++i) sums[i] = rnd(5) ? rnd(1000) : (rm_u64)rng() << 8;
-		RmDev V;
-		memset(&V, 0, sizeof(V));
-		V.scan[RM_SCAN_MEMBERS] = RmScan{1, n_tiles, 2, sums.get(), offs.get(), off.get()};      // (n: only where the totals go)
-		emu_launch(dim3(1), dim3(RM_THREADS), [&] { k_remove_tile_scan<RM_SCAN_MEMBERS>(V); });
-		for (uint32_t q = 0; q < 2; ++q) {
-			rm_u64 run = 0;
-			for (uint32_t t = 0; t <= n_tiles; ++t) { if (offs[(size_t)q * (n_tiles + 1) + t] != run) { fprintf(stderr, "remove_emu: the tile scan is off at tile %u\n", t); return 1; } if (t < n_tiles) run += sums[(size_t)q * n_tiles + t]; }
-			if (off[q * 2 + 1] != run) { fprintf(stderr, "remove_emu: the tile scan's total is off\n"); return 1; }
-		}
 	}
 	// ---- what is refused: on the host, and by the kernels before an index is derived
 	g_case = -2;
@@ -308,7 +292,7 @@ int main()
 	{ Case Z; Z.B.push_back(pga_topo_block_t{5, 9, 0, 0, 0}); Z.RB.push_back(pga_rc_block_t{nullptr, 9, 0}); RmTables R;
 	  rm_validate(1, Z.B.data(), 0, nullptr, 0, nullptr, Z.RB.data(), nullptr, nullptr, nullptr, nullptr, nullptr, 0, R); if (R.n_out_nodes || R.n_members) return 1; }
 	const rm_u64 offs[6] = {0, 2, 2, 2, 5, 5};
-	if (rm_last_le(offs, 0, 5, 0) != 0 || rm_last_le(offs, 0, 5, 1) != 0 || rm_last_le(offs, 0, 5, 2) != 3 || rm_last_le(offs, 0, 5, 4) != 3 || rm_last_le(offs, 3, 4, 4) != 3) { fprintf(stderr, "remove_emu: a lookup is off\n"); return 1; }
+	if (ts_last_le(offs, 0, 5, 0) != 0 || ts_last_le(offs, 0, 5, 1) != 0 || ts_last_le(offs, 0, 5, 2) != 3 || ts_last_le(offs, 0, 5, 4) != 3 || ts_last_le(offs, 3, 4, 4) != 3) { fprintf(stderr, "remove_emu: a lookup is off\n"); return 1; }
 	printf("remove_emu OK (%zu graphs of more than one tile, %zu blocks die, %zu members removed, %zu with long lists)\n", n_big, n_dies, n_removed, n_long);
 	return 0;
 }

@@ -52,7 +52,7 @@ static uint64_t hash_words(std::initializer_list<uint64_t> w)
 {
 	std::vector<uint8_t> b;
 	for (uint64_t x : w) for (int i = 0; i < 8; ++i) b.push_back((uint8_t)(x >> (8 * i)));
-	return dt_xxh64(b.data(), b.size(), 0);
+	return xxh64_bytes(b.data(), b.size(), 0);
 }
 struct Direct {
 	std::vector<pga_plan_match_t> matches;
@@ -384,7 +384,7 @@ int main()
 	for (int t = 0; t < 200; ++t) {
 		uint64_t w[6]; uint8_t b[48];
 		for (int i = 0; i < 6; ++i) { w[i] = t < 2 ? (uint64_t)t * ~0ULL : ((uint64_t)rng() << 32 | rng()); for (int k = 0; k < 8; ++k) b[8 * i + k] = (uint8_t)(w[i] >> (8 * k)); }
-		if (rw_xxh64_words(w, 3) != dt_xxh64(b, 24, 0) || rw_xxh64_words(w, 6) != dt_xxh64(b, 48, 0)) { printf("XXH64 of words\n"); return 1; }
+		if (xxh64_words(w, 3) != xxh64_bytes(b, 24, 0) || xxh64_words(w, 6) != xxh64_bytes(b, 48, 0)) { printf("XXH64 of words\n"); return 1; }
 	}
 	for (uint32_t x : {0u, 0x4Eu, 0x4E4E4E4Eu, 0x4E004E4Fu, 0x4D4E4F4Eu, 0xCE4E6E4Eu, 0x4E4E4E4Du}) {
 		uint32_t want = 0; for (int k = 0; k < 4; ++k) want += ((x >> (8 * k)) & 255u) == 'N';
