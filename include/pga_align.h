@@ -325,7 +325,7 @@ void pga_free(void *p);
  * edits applied to the consensus, every member's sequence rebuilt with Edit::apply and re-aligned by map_variations with the band of
  * BandParameters::from_edits).  Counting, Edit::apply, reconciliation and the re-alignment run on the device; sequences built there feed the
  * aligner without leaving it.  detach_unaligned_nodes on the realigned blocks (reconsensus.rs:85) is pga_detach_unaligned below, fed from this
- * entry's output; the node / path maps (reconsensus.rs:76-88) stay with the caller.
+ * entry's output; the node / path maps (reconsensus.rs:76-88) are pga_close_round's, further down.
  * Input: the members of block b are the next blocks[b].n_members entries of members[] (the reference's BTreeMap order), the edits of a
  * member the next n_subs / n_dels / n_inss entries of subs / dels / inss (insertion letters: ins_seq[seq_off .. seq_off + len)).
  * Output (freed with pga_rc_free): per block its kind, its consensus afterwards and its majority edits; per member (input order) its edits
@@ -653,8 +653,8 @@ void pga_topo_free(pga_topo_out_t *out);
  * pga_detach_unaligned takes the members without an aligned position out of their blocks and makes each a singleton block of its own
  * sequence.  The reference runs it on the merged blocks right after solve_promise (graph_merging.rs:154) and on the realigned blocks inside
  * reconsensus_graph (reconsensus/reconsensus.rs:85): pga_solve_promises -> pga_detach_unaligned -> pga_reconsensus -> pga_detach_unaligned
- * is that chain in one data layout.  The node map (same node id, new block id, forward strand, position kept) stays with the caller
- * (pangraph_amd/detach.py), which reads it off orphans[] and member_map[] without a search.
+ * is that chain in one data layout.  The node map (same node id, new block id, forward strand, position kept) is pga_close_round's on the
+ * flat graph; a caller that keeps dicts (pangraph_amd/detach.py) reads it off orphans[] and member_map[] without a search.
  * Blocks, members and edits in the layout of pga_reconstruct; who[m] belongs to global member m.  Inputs are only read.
  *   unaligned      Edit::aligned_count(cons_len) == 0 (edits.rs:439-442): cons_len.saturating_sub(the SUM of the deletion lengths), added
  *                  in 64 bits -- the plain sum, not the union of the intervals.  The validation admits deletions that overlap (each must
@@ -957,6 +957,102 @@ void pga_assemble_free(pga_assemble_out_t *out);
 /* Measurement only: the stream's clock over the last pga_assemble_blocks call of the calling thread that reached the device, in ms:
  * ms[0] the uploads, ms[1] the kernels with the waits between them, ms[2] the downloads. */
 void pga_assemble_last_ms(double *ms /* 3: uploads, kernels with their waits, downloads */);
+
+/* ---- self-merge: the tail of a round on the two flat layouts (self_merge, graph_merging.rs:153-169; reconsensus_graph,
+ * reconsensus/reconsensus.rs:46-91; detach_unaligned_nodes, detach_unaligned.rs:24-114) ----
+ * pga_close_round folds what pga_detach_unaligned -> pga_reconsensus -> pga_detach_unaligned returned for the merged blocks back into the
+ * flat graph of pga_plan_simplify AND the block arrays of pga_remove_paths: unaligned members leave their blocks and become singleton blocks,
+ * their nodes keep id, path and position and get the new block and the forward strand, every merged block gets its consensus and its member
+ * edits after the reconsensus.  Its output is the input of the next round.  Input, only read, taken as it stands:
+ *   blocks, paths, nodes   the graph of pga_apply_merge's output, with the rules of pga_plan_simplify.
+ *   rc_blocks, members, subs, dels, inss, ins_seq, who   the default output of pga_assemble_blocks: rc_blocks[i] is blocks[i], n_members == depth
+ *                      (0 for a dead entry); who[m] belongs to global member m = first_member[block] + member.
+ *   upd[n_upd]         the graph index of the j-th updated block: applied.new_blocks[].block of the kind-1 entries in new_blocks[] order, the
+ *                      block order of PGA_ASSEMBLE_MERGED_ONLY.  Slot s of that output's block j is slot s of graph block upd[j]: merged
+ *                      member m (block j, slot s) is global member first_member[upd[j]] + s.  The call relies on this.
+ *   detached           pga_detach_unaligned on the merged-only arrays (n_upd input blocks); read: blocks, member_map, orphans and the
+ *                      letters of the singleton blocks.
+ *   rc                 pga_reconsensus on detached's arrays, over the first n_upd blocks or all of them; read: blocks[j] for j < n_upd, the
+ *                      status of members[m1] for the members the first detach kept, cons, ins_seq.  rc_ins_seq_len: the sum of the
+ *                      n_ins_bases of those members (as p_ins_seq_len is for pga_assemble_blocks).
+ *   redetached         the second pga_detach_unaligned, on the arguments pga_rc_detach_args builds from rc (its subs, dels, inss and ins_seq
+ *                      are rc's own arrays by pointer: they are already dense in member order), over all n_upd blocks (the
+ *                      reference runs it on the kind-2 blocks only; a kind-0 or kind-1 block keeps cons_len and every deletion and the
+ *                      first detach has taken its unaligned members, so the result is the same, and an orphan of redetached in a block
+ *                      whose kind is not 2 fails the call); read: blocks, members, subs, dels, inss, member_map, orphans, the letters.
+ * The member chain: detached->member_map[m] is an orphan or member m1 of the second stage, redetached->member_map[m1] an orphan or a final
+ * member; a final member's slot is its rank among the members of block j that redetached kept (relative order, so node-id order, is kept).
+ * Output (freed with pga_close_free), all exact integers:
+ *   blocks[]           alive blocks only, strictly ascending unsigned block_id, dead entries dropped (as pga_apply_merge drops them), the
+ *                      singleton blocks merged in by id.  An updated block keeps its id; cons_len = rc->blocks[j].cons_len, depth = the
+ *                      members redetached kept (a block left without a member stays alive with depth 0, as in the reference).  A singleton:
+ *                      block_id and len of the orphan record, depth 1.  block_map[input index] = index after, UINT32_MAX for a dead entry.
+ *   paths[]            copied.  nodes[]: same count and order; a node of a block that is not updated keeps its slot (block translated by
+ *                      block_map), a final member's node gets its slot, an orphan's node block = the singleton's index, member = 0,
+ *                      reverse = 0; node_id, pos0 and pos1 never change.
+ *   rc_blocks, members, subs, dels, inss   rc_blocks[i] is blocks[i] after; members block after block, the three lists dense in that order.
+ *                      Survivors are copied from the arrays given, an updated block's members and lists come from redetached, a singleton
+ *                      has one member with the counts 0, 0, 0.
+ *   ins_seq            always gathered in output order (n_ins_letters), seq_off the running sum of len.  Sources: the caller's ins_seq and
+ *                      rc->ins_seq (redetached's insertions point into it); a source seq_off may be in any order and may overlap.
+ *   cons               the consensus letters this call owns, every sequence at a multiple of 16 (n_cons_letters: the bytes used, padding
+ *                      included), in block order after: the updated blocks of kind 1 and 2 (from rc->cons) and the singletons (from
+ *                      detached->cons / redetached->cons).  A kind-0 block and every other block keep the pointer they had.
+ *                      PGA_CLOSE_COPY_CONSENSUS: every alive block's letters are copied there (a host copy on the library's thread ranges);
+ *                      afterwards only `out` must live on.  Without it the caller's consensus buffers go on serving.
+ *   who[m], origin[m]  every member after is exactly one member before: origin[m] its global member in the arrays given, who[m] that
+ *                      member's entry, with reverse = 0 for an orphan.
+ *   kinds[j]           rc->blocks[j].kind.  orphans[]: the records of detached, then of redetached, with member = the global member in the
+ *                      arrays given and block = the singleton's index after.
+ *   (n_blocks, blocks, n_paths, paths, n_nodes, nodes) are the first six arguments of the next pga_apply_merge, of pga_plan_simplify,
+ *   pga_remove_paths and the exports; (n_blocks, rc_blocks, members, subs, dels, inss, ins_seq) with n_ins_letters the first arguments of the
+ *   next pga_assemble_blocks, of pga_reconstruct, pga_merge_blocks, pga_remove_paths and pga_export_json; who is the member-to-node map those
+ *   entries assume: pointers only.
+ * n_upd == 0 (detached, rc, redetached may be NULL) returns the input copied, with compacted letters, dead entries dropped and the identity
+ * maps.  n_blocks == 0: no device call.
+ * Malformed input fails the call (-1, message in pga_last_error(), out zeroed).  Before anything is launched: what pga_plan_simplify refuses
+ * about the graph on the host, rc_blocks[i].n_members != depth or rc_blocks[i].cons_len != blocks[i].cons_len of an alive block, a kind-0 block
+ * whose rc cons_len is not the one it had, an orphan record k of a stage whose block is not n_upd + k or whose len is not that block's
+ * cons_len (the letters of orphan k are read there), a NULL array with a non-zero count, an unknown flag, upd[j] out of range,
+ * dead or named twice, detached->n_blocks != n_upd + detached->n_orphans (the same for redetached), kept members plus orphans of a stage
+ * not summing to the members it was given, rc->blocks[j].kind < 0 (the reference's Err; the message names the block and the kind), a
+ * rc->members[] entry of a read member with status != 0 (edit_consensus_and_realign returns Err; the message names block and member), an
+ * orphan record with status != 0 (create_new_node_and_block's Err), 2^31 or more blocks, members or nodes after, edit totals that overflow
+ * 2^63.  On the device, before any index derived from it is used: kept members plus orphans of block j not equal to its depth, in either
+ * stage; a member_map that is no bijection onto the stage's places or does not keep the order; an orphan of the second stage in a block
+ * whose kind is not 2; a singleton block_id equal to a surviving block's or another singleton's (the reference panics "Conflicting key" on
+ * the first route and would overwrite on the second; both are refused); a graph slot named by no node or by two; seq_off + len beyond
+ * ins_seq_len / rc_ins_seq_len (before a letter is read; a NULL buffer has length 0).
+ * The call waits for the device three times: the checks and list totals, the letter checks and total, the output. */
+#define PGA_CLOSE_COPY_CONSENSUS 1u
+typedef struct {
+	int64_t n_blocks, n_paths, n_nodes, n_members, n_orphans;
+	uint64_t n_subs, n_dels, n_inss, n_ins_letters, n_cons_letters;
+	pga_topo_block_t *blocks; pga_topo_path_t *paths; pga_topo_node_t *nodes;      /* the graph after, pga_plan_simplify's layout */
+	pga_rc_block_t *rc_blocks; pga_rc_member_t *members; pga_sub_t *subs; pga_del_t *dels; pga_ins_t *inss; char *ins_seq;
+	char *cons;                      /* consensus letters this call owns, every sequence at a multiple of 16 */
+	pga_detach_member_t *who;        /* per member after: node id, strand */
+	int64_t *origin;                 /* per member after: its global member in the block arrays given */
+	uint32_t *block_map;             /* [input blocks] index after, UINT32_MAX for a dead entry */
+	int32_t *kinds;                  /* [n_upd] the reconsensus kind of every updated block */
+	pga_detach_orphan_t *orphans;    /* [n_orphans] first detach's, then second's; member = global member of the arrays given, block = index after */
+} pga_close_out_t;
+int  pga_close_round(int64_t n_blocks, const pga_topo_block_t *blocks, int64_t n_paths, const pga_topo_path_t *paths, int64_t n_nodes, const pga_topo_node_t *nodes,
+                     const pga_rc_block_t *rc_blocks, const pga_rc_member_t *members, const pga_sub_t *subs, const pga_del_t *dels, const pga_ins_t *inss,
+                     const char *ins_seq, uint64_t ins_seq_len, const pga_detach_member_t *who,
+                     int64_t n_upd, const uint32_t *upd,
+                     const pga_detach_out_t *detached, const pga_rc_out_t *rc, uint64_t rc_ins_seq_len, const pga_detach_out_t *redetached,
+                     uint32_t flags, pga_close_out_t *out);
+void pga_close_free(pga_close_out_t *out);
+/* Measurement only: the stream's clock over the last pga_close_round call of the calling thread that reached the device, in ms. */
+void pga_close_last_ms(double *ms /* 3: uploads, kernels with their waits, downloads */);
+/* pga_rc_detach_args (host only) fills the first arguments of the SECOND pga_detach_unaligned call from a pga_rc_out_t:
+ * blocks[j] = {rc->cons + cons_off, cons_len, detached->blocks[j].n_members} for j < n_upd, members[m1] = the three counts of rc->members[m1]
+ * for the members the first detach kept, who2[detached->member_map[m]] = who_merged[m] for every kept m.  rc->subs, dels, inss and ins_seq
+ * are already dense in member order (pga_reconsensus.hip, the pack loop) and go into that call by pointer, as they stand.
+ * Returns 0, or -1 with the message in pga_last_error(). */
+int pga_rc_detach_args(int64_t n_upd, const pga_detach_out_t *detached, const pga_detach_member_t *who_merged, const pga_rc_out_t *rc,
+                       pga_rc_block_t *blocks /* [n_upd] */, pga_rc_member_t *members /* [kept members] */, pga_detach_member_t *who2);
 
 /* ---- export gfa (io/gfa.rs:79-279 gfa_write / convert_pangraph_to_gfa, Edge of circularize/circularize_utils.rs:46-102) ----
  * pga_export_gfa writes, for the flat graph of pga_plan_simplify (blocks, paths, nodes: its rules, only read) and GfaWriteParams, the bytes

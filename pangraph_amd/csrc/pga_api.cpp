@@ -1466,6 +1466,47 @@ extern "C" int pga_assemble_blocks(int64_t n_blocks, const pga_rc_block_t *rc_bl
 	} catch (std::exception &e) { pga_assemble_free(out); set_err(e.what()); return -1; }
 }
 
+// ---------------------------------------------------------------- the tail of a self-merge round on the flat graph (pga_close.hip)
+namespace pga {
+void close_round_host(int64_t n_blocks, const pga_topo_block_t *blocks, int64_t n_paths, const pga_topo_path_t *paths, int64_t n_nodes, const pga_topo_node_t *nodes,
+                      const pga_rc_block_t *rc_blocks, const pga_rc_member_t *members, const pga_sub_t *subs, const pga_del_t *dels, const pga_ins_t *inss,
+                      const char *ins_seq, uint64_t ins_seq_len, const pga_detach_member_t *who, int64_t n_upd, const uint32_t *upd,
+                      const pga_detach_out_t *detached, const pga_rc_out_t *rc, uint64_t rc_ins_seq_len, const pga_detach_out_t *redetached,
+                      uint32_t flags, pga_close_out_t *out);
+void rc_detach_args_host(int64_t n_upd, const pga_detach_out_t *detached, const pga_detach_member_t *who_merged, const pga_rc_out_t *rc,
+                         pga_rc_block_t *blocks, pga_rc_member_t *members, pga_detach_member_t *who2);
+void close_last_ms(double *ms);
+}
+extern "C" void pga_close_free(pga_close_out_t *o)
+{
+	if (!o) return;
+	free(o->blocks); free(o->paths); free(o->nodes); free(o->rc_blocks); free(o->members); free(o->subs); free(o->dels); free(o->inss); free(o->ins_seq);
+	free(o->cons); free(o->who); free(o->origin); free(o->block_map); free(o->kinds); free(o->orphans);
+	memset(o, 0, sizeof(*o));
+}
+extern "C" void pga_close_last_ms(double *ms) { if (ms) pga::close_last_ms(ms); }
+extern "C" int pga_close_round(int64_t n_blocks, const pga_topo_block_t *blocks, int64_t n_paths, const pga_topo_path_t *paths, int64_t n_nodes, const pga_topo_node_t *nodes,
+                               const pga_rc_block_t *rc_blocks, const pga_rc_member_t *members, const pga_sub_t *subs, const pga_del_t *dels, const pga_ins_t *inss,
+                               const char *ins_seq, uint64_t ins_seq_len, const pga_detach_member_t *who, int64_t n_upd, const uint32_t *upd,
+                               const pga_detach_out_t *detached, const pga_rc_out_t *rc, uint64_t rc_ins_seq_len, const pga_detach_out_t *redetached,
+                               uint32_t flags, pga_close_out_t *out)
+{
+	if (!out) { set_err("pga_close_round: null output"); return -1; }
+	memset(out, 0, sizeof(*out));
+	try {
+		if (n_blocks > 0) require_device();
+		pga::close_round_host(n_blocks, blocks, n_paths, paths, n_nodes, nodes, rc_blocks, members, subs, dels, inss, ins_seq, ins_seq_len, who, n_upd, upd, detached, rc,
+		                      rc_ins_seq_len, redetached, flags, out);
+		return 0;
+	} catch (std::exception &e) { pga_close_free(out); set_err(e.what()); return -1; }
+}
+extern "C" int pga_rc_detach_args(int64_t n_upd, const pga_detach_out_t *detached, const pga_detach_member_t *who_merged, const pga_rc_out_t *rc,
+                                  pga_rc_block_t *blocks, pga_rc_member_t *members, pga_detach_member_t *who2)
+{
+	try { pga::rc_detach_args_host(n_upd, detached, who_merged, rc, blocks, members, who2); return 0; }
+	catch (std::exception &e) { set_err(e.what()); return -1; }
+}
+
 // ---------------------------------------------------------------- export gfa (pga_gfa.hip)
 namespace pga {
 void export_gfa_host(int64_t n_blocks, const pga_topo_block_t *blocks, int64_t n_paths, const pga_topo_path_t *paths, int64_t n_nodes, const pga_topo_node_t *nodes,
