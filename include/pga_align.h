@@ -1054,6 +1054,67 @@ void pga_close_last_ms(double *ms /* 3: uploads, kernels with their waits, downl
 int pga_rc_detach_args(int64_t n_upd, const pga_detach_out_t *detached, const pga_detach_member_t *who_merged, const pga_rc_out_t *rc,
                        pga_rc_block_t *blocks /* [n_upd] */, pga_rc_member_t *members /* [kept members] */, pga_detach_member_t *who2);
 
+/* ---- graph_join on the two flat layouts (graph_merging.rs:74-93: the first line of merge_graphs at every internal node of the guide tree) ----
+ * pga_join_graphs puts n_parts graphs into one: the union of their blocks, paths and nodes in the order the reference's BTreeMaps give, a
+ * "Conflicting key" refusal on a shared block, path or node id.  A part is one graph in both layouts, exactly as pga_close_out_t hands it on,
+ * and is only read:
+ *   n_blocks, blocks, n_paths, paths, n_nodes, nodes   the graph in pga_plan_simplify's layout and under its rules; dead entries are allowed.
+ *   rc_blocks, members, subs, dels, inss, ins_seq, ins_seq_len, who   the block arrays: rc_blocks[i] is blocks[i], n_members == depth (0 for a
+ *                      dead entry), the three lists dense in member order, who[m] belongs to global member m.
+ * Output (freed with pga_join_free), all exact integers:
+ *   blocks[]           the alive blocks of all parts in strictly ascending unsigned block_id, dead entries dropped.  block_map[] runs over the
+ *                      input blocks of all parts behind each other (part p's at block_map_off[p], block_map_off[n_parts] entries in all):
+ *                      the index after, UINT32_MAX for a dead entry.
+ *   paths[]            ascending path_id, node_off the running sum; path_map[] / path_map_off[] in the same way.
+ *   nodes[]            path after path in that order, each path's nodes in their own order; block is translated by block_map, member,
+ *                      reverse, node_id, pos0 and pos1 are unchanged.
+ *   rc_blocks, members, subs, dels, inss   rc_blocks[i] is blocks[i] after; members block after block, inside a block the slots as they were
+ *                      (a block belongs to one part); the three lists dense in that order.
+ *   ins_seq            always gathered in output order (n_ins_letters), seq_off the running sum of len; a source seq_off may be in any order
+ *                      and may overlap.
+ *   cons               by default empty: every consensus pointer is the part's own, so the parts' letters go on serving.
+ *                      PGA_JOIN_COPY_CONSENSUS: every block's letters are copied there, every sequence at a multiple of 16 (a host copy on
+ *                      the library's thread ranges); afterwards only `out` must live on.  No consensus letter goes to the device.
+ *   who[m], origin_part[m], origin[m]   member m after is global member origin[m] of part origin_part[m]; who[m] is that member's entry.
+ *   (n_blocks, blocks, n_paths, paths, n_nodes, nodes) and (n_blocks, rc_blocks, members, subs, dels, inss, ins_seq) with n_ins_letters and
+ *   who are, by pointer, the first arguments of pga_apply_merge, pga_assemble_blocks, pga_plan_simplify, pga_remove_paths, pga_reconstruct,
+ *   the exports -- and a part of the next pga_join_graphs.
+ * n_parts == 1 gives the compacted copy with the identity origin.  A part with n_blocks == 0 is legal; when no part has a block or a path
+ * there is no device call.
+ * Malformed input fails the call (-1, message in pga_last_error(), out zeroed); every message names the part.  Before anything is launched,
+ * per part: what pga_plan_simplify refuses about the graph on the host (ids not ascending, a node naming a dead or out-of-range block,
+ * member >= depth, node_off not the running sum), rc_blocks[i].n_members != depth or a cons_len mismatch of an alive block, a NULL array with
+ * a non-zero count; an unknown flag, n_parts < 1, 2^31 or more blocks, members, nodes or paths, edit totals that overflow 2^63.  On the
+ * device, before any index derived from it is used: a block id, a path id or a node id present twice, across parts or within one (the
+ * reference's "Conflicting key" panic; the message names the kind, the smallest such id and the parts); a (block, member) slot of a part
+ * named by no node or by two; seq_off + len of an insertion beyond its own part's ins_seq_len (a NULL buffer has length 0), so an insertion
+ * of one part never reads another part's letters.
+ * The call waits for the device three times: the checks and list totals, the letter checks and total, the output. */
+#define PGA_JOIN_COPY_CONSENSUS 1u
+typedef struct {
+	int64_t n_blocks; const pga_topo_block_t *blocks; int64_t n_paths; const pga_topo_path_t *paths; int64_t n_nodes; const pga_topo_node_t *nodes;
+	const pga_rc_block_t *rc_blocks; const pga_rc_member_t *members; const pga_sub_t *subs; const pga_del_t *dels; const pga_ins_t *inss;
+	const char *ins_seq; uint64_t ins_seq_len; const pga_detach_member_t *who;
+} pga_join_part_t;
+typedef struct {
+	int64_t n_blocks, n_paths, n_nodes, n_members, n_parts;
+	uint64_t n_subs, n_dels, n_inss, n_ins_letters, n_cons_letters;
+	pga_topo_block_t *blocks; pga_topo_path_t *paths; pga_topo_node_t *nodes;      /* the graph after, pga_plan_simplify's layout */
+	pga_rc_block_t *rc_blocks; pga_rc_member_t *members; pga_sub_t *subs; pga_del_t *dels; pga_ins_t *inss; char *ins_seq;
+	char *cons;                      /* PGA_JOIN_COPY_CONSENSUS: every block's letters, every sequence at a multiple of 16 */
+	pga_detach_member_t *who;        /* per member after: node id, strand */
+	int32_t *origin_part;            /* per member after: the part it came from */
+	int64_t *origin;                 /* per member after: its global member in that part's block arrays */
+	uint32_t *block_map;             /* [block_map_off[n_parts]] index after, UINT32_MAX for a dead entry */
+	uint64_t *block_map_off;         /* [n_parts + 1] */
+	uint32_t *path_map;              /* [path_map_off[n_parts]] index after */
+	uint64_t *path_map_off;          /* [n_parts + 1] */
+} pga_join_out_t;
+int  pga_join_graphs(int32_t n_parts, const pga_join_part_t *parts, uint32_t flags, pga_join_out_t *out);
+void pga_join_free(pga_join_out_t *out);
+/* Measurement only: the stream's clock over the last pga_join_graphs call of the calling thread that reached the device, in ms. */
+void pga_join_last_ms(double *ms /* 3: uploads, kernels with their waits, downloads */);
+
 /* ---- export gfa (io/gfa.rs:79-279 gfa_write / convert_pangraph_to_gfa, Edge of circularize/circularize_utils.rs:46-102) ----
  * pga_export_gfa writes, for the flat graph of pga_plan_simplify (blocks, paths, nodes: its rules, only read) and GfaWriteParams, the bytes
  * gfa_write_str gives, and returns the tables behind them.  By the reference:

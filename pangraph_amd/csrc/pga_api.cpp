@@ -1507,6 +1507,32 @@ extern "C" int pga_rc_detach_args(int64_t n_upd, const pga_detach_out_t *detache
 	catch (std::exception &e) { set_err(e.what()); return -1; }
 }
 
+// ---------------------------------------------------------------- graph_join on the two flat layouts (pga_join.hip)
+namespace pga {
+void join_graphs_host(int32_t n_parts, const pga_join_part_t *parts, uint32_t flags, pga_join_out_t *out);
+void join_last_ms(double *ms);
+}
+extern "C" void pga_join_free(pga_join_out_t *o)
+{
+	if (!o) return;
+	free(o->blocks); free(o->paths); free(o->nodes); free(o->rc_blocks); free(o->members); free(o->subs); free(o->dels); free(o->inss); free(o->ins_seq);
+	free(o->cons); free(o->who); free(o->origin_part); free(o->origin); free(o->block_map); free(o->block_map_off); free(o->path_map); free(o->path_map_off);
+	memset(o, 0, sizeof(*o));
+}
+extern "C" void pga_join_last_ms(double *ms) { if (ms) pga::join_last_ms(ms); }
+extern "C" int pga_join_graphs(int32_t n_parts, const pga_join_part_t *parts, uint32_t flags, pga_join_out_t *out)
+{
+	if (!out) { set_err("pga_join_graphs: null output"); return -1; }
+	memset(out, 0, sizeof(*out));
+	try {
+		bool any = false;
+		for (int32_t p = 0; parts && p < n_parts; ++p) any = any || parts[p].n_blocks > 0 || parts[p].n_paths > 0;
+		if (any) require_device();
+		pga::join_graphs_host(n_parts, parts, flags, out);
+		return 0;
+	} catch (std::exception &e) { pga_join_free(out); set_err(e.what()); return -1; }
+}
+
 // ---------------------------------------------------------------- export gfa (pga_gfa.hip)
 namespace pga {
 void export_gfa_host(int64_t n_blocks, const pga_topo_block_t *blocks, int64_t n_paths, const pga_topo_path_t *paths, int64_t n_nodes, const pga_topo_node_t *nodes,
